@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- projections/sec (fwd+adj) of the Radon projector on synthetic 128x128 foam, 20 sparse angles.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,8 @@ A step = one pass of the hot path over one batch: rotate-and-sum forward (neares
 project_tf_fast) followed by the backward TensorFlow runs for it (tf_compat), on B=50 objects per GPU that are
 already resident in HBM (BASELINE.json configs[1]).  The batch shards over ranks with no data-path collective
 (weak scaling: 50 objects per GPU).  Rank 0 prints ONE JSON line; see DESIGN.md section "Measurement".
+A plain run sets up, warms up, times exactly K steps and prints the headline; --full adds every other figure
+(per-kernel times and the roofline, the autograd API path, the four modes, cold inputs, the CPU baseline).
 """
 import argparse
 import json
@@ -39,9 +41,16 @@ def parse():
     ap.add_argument("--angles", type=int, default=A_SPARSE, help="20 (headline) or 180 (dense evaluation set)")
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="objects per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--min-ms", type=float, default=50.0,
+    ap.add_argument("--min-ms", type=float, default=None,
                     help="the K-step timed region is repeated until this much time has been measured in all; the median "
-                         "region is reported (steps stays K)")
+                         "region is reported (steps stays K).  Default: 0 (one region of exactly K steps), 50 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="projector mode: everything beside the headline as well -- per-kernel launch times and the roofline, "
+                         "the spread of single steps, the autograd API path, the four (interp x backward) modes, the "
+                         "cold-input figure, the CPU baseline and, with N > 1, the same steps with the gradient all-reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="projector mode: after the timed steps, write what the last one computed (the sinogram and the "
+                         "gradient image) as DIR/<name>.npy, float32, at most 64 MB in all (a seeded sample of objects beyond)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the all-cores CPU baseline (0: the cores this process may run on, at most 16 -- the "
                          "CPU share of a one-GPU box)")
@@ -72,6 +81,23 @@ def parse():
     ap.add_argument("--n512-batch", type=int, default=32,
                     help="objects per GPU in --mode n512 (32: 768 tile workgroups = 3 full rounds on 256 CUs; 8: 192)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_BYTES):
+    """Write every tensor of `arrays` (name -> fp32 tensor, objects on axis 0) as out_dir/<name>.npy.  When they hold more than
+    `limit` bytes in all, each keeps the same fixed, seeded choice of objects, in proportion: runs with the same arguments
+    write the same sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if total > limit:
+            keep = max(1, a.shape[0] * limit // total)
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def self_launch(n_gpus):
@@ -523,6 +549,10 @@ def project_scaling_mode(args, dev):
 
 def main():
     args = parse()
+    if args.min_ms is None:
+        args.min_ms = 50.0 if args.full else 0.0
+    if args.dump_outputs and (args.mode != "projector" or args.project_scaling):
+        raise SystemExit("--dump-outputs writes the outputs of the projector mode's timed step")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     world, rank, local = dist_setup(args.gpus)
@@ -604,13 +634,52 @@ def main():
             step()
         return close_timed_region(t0, world)
 
-    # One region of K = 20 steps lasts 0.3 ms: too short to hang a headline on.  The region is therefore repeated until
-    # --min-ms of measured time has accumulated (every rank takes the same decision: the region times are already
-    # maxima over ranks) and the MEDIAN region is reported; `steps` stays K, `repeats` says how many regions were timed.
+    # A plain run times ONE region of exactly K steps.  One region of K = 20 steps lasts 0.3 ms: too short to hang a headline
+    # on, so --min-ms (50 ms with --full) repeats the region until that much time has accumulated (every rank takes the same
+    # decision: the region times are already maxima over ranks) and the MEDIAN region is reported; `steps` stays K, `repeats`
+    # says how many regions were timed.
     regions = [timed_region()]
     while sum(regions) * 1e3 < args.min_ms and len(regions) < 10000:
         regions.append(timed_region())
     elapsed = float(np.median(regions))
+    if args.dump_outputs:      # before anything else launches into sino / gimg
+        suffix = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"sinogram" + suffix: sino, "grad_image" + suffix: gimg}, DUMP_BYTES // world)
+
+    from ct_pvae_amd import _lib
+    tune_env = {k: v for k, v in os.environ.items() if k.startswith("CTPVAE_")}
+    total_objects = args.total_batch if strong else world * B
+    proj_per_s = total_objects * A * args.steps / elapsed
+    bytes_dir = 4.0 * B * (N * N + A * P)                 # one direction: read once + write once (fp32)
+    out = {
+        "metric": "projections/sec (fwd+adj) 128x128 foam, 20 angles; fraction of HBM roofline",
+        "value": proj_per_s, "unit": "projections/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "repeats": len(regions),
+        "region_ms": {"min": min(regions) * 1e3, "median": elapsed * 1e3, "max": max(regions) * 1e3,
+                      "what": f"{len(regions)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both "
+                              "sides, max over ranks); value and ms_per_step are from the median region"},
+        "developer_knobs": {"library_knobs_set": _lib.load().ctpvae_tune_active(), "env": tune_env},
+        "config": {"workload": (f"total batch {args.total_batch} shared by {world} GPU(s) ({B} on rank 0), " if strong else f"batch={B}/GPU ")
+                               + f"{N}x{N} foam, {A} angles, P={P}, rotate nearest fwd + tf_compat adj",
+                   "objects_per_gpu": B, "n_pixel": N, "angles": A, "num_proj_pix": P, "parallelism": f"batch-shard x{world}",
+                   "inputs": (f"cold: {n_cold} distinct batches cycled, {n_cold * (x.numel() + g.numel()) * 4 / 1e6:.0f} MB > the "
+                              "256 MB Infinity Cache" if args.cold else
+                              "cache-warm: ONE resident batch re-projected every step (3.3 MB of objects + 0.7 MB of cotangents "
+                              "stay in the Infinity Cache; --cold cycles 96 distinct batches)"),
+                   "forward_plan": "compact (2 bits per row)" if plan.dense_plan(B)[1] else "u16 taps",
+                   "grad_allreduce_bytes_per_step": 4 * 711164 if args.grad_allreduce else 0,
+                   "launch": (f"{n_replay} replays of a HIP graph of {chunk} steps + {n_eager} steps launched from Python"
+                              if graph is not None else "every step launched from Python")},
+        "ray_sums_per_s_per_gpu": proj_per_s * P / world,
+        "hbm_fraction_whole_step": (2 * bytes_dir / (elapsed / args.steps)) / 1e9 / HBM_PEAK_GBS,
+    }
+    if not args.full:          # the headline alone: everything below takes runs of its own
+        if rank == 0:
+            print(json.dumps(out))
+        return
 
     # ---- multi-GPU: the same K steps WITH the data-parallel trainer's one collective ------------------------------------
     # north_star: "batches of objects shard across the GPUs of one node with RCCL all-reduce of VAE gradients".  The projector
@@ -773,7 +842,6 @@ def main():
 
     if rank != 0:
         return
-    bytes_dir = 4.0 * B * (N * N + A * P)                 # one direction: read once + write once (fp32)
     fwd_name = plan.forward_kernel_name(B)
     bwd_name = plan.backward_kernel_name(B)
     dom = (fwd_name, t_fwd) if t_fwd >= t_bwd else (bwd_name, t_bwd)
@@ -788,39 +856,12 @@ def main():
         _, _, lds_fwd = committed_counters("" if A == 20 else "angles180_", fwd_name, B * A * P * P, t_fwd)
         if lds_fwd is not None and dom[0] != fwd_name:
             lds = dict(lds or {}, forward=lds_fwd)
-    from ct_pvae_amd import _lib
-    tune_env = {k: v for k, v in os.environ.items() if k.startswith("CTPVAE_")}
-    total_objects = args.total_batch if strong else world * B
-    proj_per_s = total_objects * A * args.steps / elapsed
     # the four (interp x backward) modes and the cold-input figure beside the headline (one GPU, the headline shape)
     modes, cold = None, None
     if world == 1 and not args.no_modes and not args.cold and not strong:
         modes = four_modes(theta, B, N, A, dev, x, g)
         cold = cold_figure(plan, x, g, sino, gimg, B, A)
-    out = {
-        "metric": "projections/sec (fwd+adj) 128x128 foam, 20 angles; fraction of HBM roofline",
-        "value": proj_per_s, "unit": "projections/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "repeats": len(regions),
-        "region_ms": {"min": min(regions) * 1e3, "median": elapsed * 1e3, "max": max(regions) * 1e3,
-                      "what": f"{len(regions)} timed regions of exactly {args.steps} steps each (barrier + synchronize on both "
-                              "sides, max over ranks); value and ms_per_step are from the median region"},
-        "developer_knobs": {"library_knobs_set": _lib.load().ctpvae_tune_active(), "env": tune_env},
-        "config": {"workload": (f"total batch {args.total_batch} shared by {world} GPU(s) ({B} on rank 0), " if strong else f"batch={B}/GPU ")
-                               + f"{N}x{N} foam, {A} angles, P={P}, rotate nearest fwd + tf_compat adj",
-                   "objects_per_gpu": B, "n_pixel": N, "angles": A, "num_proj_pix": P, "parallelism": f"batch-shard x{world}",
-                   "inputs": (f"cold: {n_cold} distinct batches cycled, {n_cold * (x.numel() + g.numel()) * 4 / 1e6:.0f} MB > the "
-                              "256 MB Infinity Cache" if args.cold else
-                              "cache-warm: ONE resident batch re-projected every step (3.3 MB of objects + 0.7 MB of cotangents "
-                              "stay in the Infinity Cache; --cold cycles 96 distinct batches)"),
-                   "forward_plan": "compact (2 bits per row)" if plan.dense_plan(B)[1] else "u16 taps",
-                   "grad_allreduce_bytes_per_step": 4 * 711164 if args.grad_allreduce else 0,
-                   "launch": (f"{n_replay} replays of a HIP graph of {chunk} steps + {n_eager} steps launched from Python"
-                              if graph is not None else "every step launched from Python")},
-        "ray_sums_per_s_per_gpu": proj_per_s * P / world,
-        "hbm_fraction_whole_step": (2 * bytes_dir / (elapsed / args.steps)) / 1e9 / HBM_PEAK_GBS,
+    out.update({
         "roofline": {"bound": "hbm", "kernel": dom[0], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy": achieved / HBM_COPY_GBS,
                      "traffic": traffic, "traffic_source": traffic_source, "lds": lds, "algorithmic_bytes_per_launch": bytes_dir,
@@ -830,7 +871,7 @@ def main():
         "step_us_event_pairs": {"p10": float(np.percentile(step_us, 10)), "median": float(np.median(step_us)),
                                 "p90": float(np.percentile(step_us, 90)), "n": len(step_us)},
         "api": api,
-    }
+    })
     if modes is not None:
         out["modes"] = modes
         out["cold"] = cold

@@ -1268,7 +1268,7 @@ def test_bench_under_torchrun_two_ranks():
     env = dict(os.environ, CTPVAE_REHEARSE_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30",
-           "--warmup", "5", "--grad-allreduce"]      # config 4's collective rides along (2.8 MB bucket per step)
+           "--warmup", "5", "--grad-allreduce", "--full"]      # config 4's collective rides along (2.8 MB bucket per step)
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1294,7 +1294,7 @@ def test_bench_launches_its_own_ranks():
     from tests.conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--min-ms", "5"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--min-ms", "5", "--full"], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -1622,13 +1622,13 @@ def test_launches_are_graph_capturable():
 
 
 def test_bench_single_process_contract():
-    """`python bench.py` as the driver runs it at N = 1 (few steps here): one JSON line with the contract's keys, the
-    roofline and cpu_baseline objects, traffic from the committed PMC passes for the default workload."""
+    """`python bench.py --full` at N = 1 (few steps here): one JSON line with the contract's keys, the roofline and
+    cpu_baseline objects, traffic from the committed PMC passes for the default workload."""
     import json
     import subprocess
     import sys
     from tests.conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "60", "--warmup", "10", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1642,7 +1642,7 @@ def test_bench_single_process_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and "sample" in c
     assert d["value"] > 1e7                      # tens of millions of projections per second on an MI355X
-    # round 5: all four (interp x backward) modes and the cold-input figure ride in the driver's line
+    # round 5: all four (interp x backward) modes and the cold-input figure ride in the --full line
     m = d["modes"]
     assert {"nearest_tf_compat", "nearest_exact", "bilinear_tf_compat", "bilinear_exact"} <= set(m)
     for k in ("nearest_tf_compat", "nearest_exact", "bilinear_tf_compat", "bilinear_exact"):
@@ -1650,6 +1650,33 @@ def test_bench_single_process_contract():
         assert abs(m[k]["hbm_frac"]["fwd"] - 4.0 * 50 * (128 * 128 + 20 * 184) / (m[k]["fwd_us"] * 1e-6) / 8e12) < 1e-9
     assert m["bilinear_exact"]["bwd_us"] < 40.0          # the scatter kernel took 367 us (profiles/r05_modes_baseline_*)
     assert 0.5 * d["value"] < d["cold"]["value"] <= 1.1 * d["value"] and d["cold"]["ms_per_step"] > 0
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps K` without --full: ONE timed region of exactly K steps and the headline alone; --dump-outputs
+    writes what the last timed step computed from the seeded inputs -- the sinogram and the gradient image, the bits the
+    same plan gives here."""
+    import json
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--dump-outputs",
+                          str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 40 and d["warmup"] == 5 and d["repeats"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] - 50 * 20 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    assert not {"roofline", "api", "modes", "cold", "cpu_baseline", "step_us_event_pairs"} & set(d)
+    sino, gimg = np.load(tmp_path / "sinogram.npy"), np.load(tmp_path / "grad_image.npy")
+    assert sino.dtype == np.float32 and sino.shape == (50, 20, 184) and gimg.dtype == np.float32 and gimg.shape == (50, 128, 128)
+    d_ = dev()
+    theta = phantoms.dense_theta(180)[phantoms.sparse_angle_indices(180, 20)]
+    plan = RotatePlan(theta, 128, 128, True, d_, interp="nearest", backward="tf_compat")
+    x = torch.from_numpy(phantoms.foam_batch(50, 128, seed=0, supersample=2)).to(d_)
+    g = torch.from_numpy(np.random.default_rng(1000).standard_normal((50, 20, 184)).astype(np.float32)).to(d_)
+    assert np.array_equal(sino, to_np(plan.forward(x))) and np.array_equal(gimg, to_np(plan.backward(g)))
 
 
 def test_bench_strong_scaling_two_ranks_and_projection():

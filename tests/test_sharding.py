@@ -34,6 +34,9 @@ def _free_port():
 def _worker(rank, world, port, tmp):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank),
                       LOCAL_RANK=str(rank))
+    # the host path, as on a machine without a GPU, wherever the suite runs: on a one-GPU box rank 1 would otherwise bind a
+    # device that does not exist (the rehearsal of two ranks on one GPU is tests/test_gpu_parity.py's bench tests)
+    torch.cuda.is_available = lambda: False
     w, r, _ = sharding.init_from_env(backend="gloo")
     assert (w, r) == (world, rank)
     # (1) timing aggregation: max over ranks; object count: sum over ranks

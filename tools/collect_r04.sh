@@ -20,7 +20,7 @@ traffic() { # traffic <name> <program + args...>: two PMC passes -> <name>_traff
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pmcw_$name -o w -- "$@" > "$OUT/$name.write.log" 2>&1
   python3 "$ROOT/tools/pmc_to_json.py" traffic "$(find /tmp/pmcf_$name -name '*.db' | head -1)" "$(find /tmp/pmcw_$name -name '*.db' | head -1)" > "$OUT/${name}_traffic_pmc.json"
 }
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 for part in $PARTS; do case $part in
 bench)
   $B > "$OUT/bench.json" 2> "$OUT/bench.err"
@@ -32,17 +32,17 @@ bench)
   $B --mode train --steps 100 --no-cpu-baseline > "$OUT/bench_modetrain.json" 2>> "$OUT/bench.err"
   ;;
 stats)
-  stats bench python3 "$ROOT/bench.py" --no-cpu-baseline
-  stats angles180 python3 "$ROOT/bench.py" --no-cpu-baseline --angles 180
-  stats moden512 python3 "$ROOT/bench.py" --no-cpu-baseline --mode n512
+  stats bench python3 "$ROOT/bench.py" --full --no-cpu-baseline
+  stats angles180 python3 "$ROOT/bench.py" --full --no-cpu-baseline --angles 180
+  stats moden512 python3 "$ROOT/bench.py" --full --no-cpu-baseline --mode n512
   stats training_call python3 "$ROOT/tools/trace_training_call.py" 50
   stats setup_path python3 "$ROOT/tools/time_recon.py"
   ;;
 traffic)
-  traffic bench python3 "$ROOT/bench.py" --steps 50 --warmup 10 --no-cpu-baseline
-  traffic angles180 python3 "$ROOT/bench.py" --steps 50 --warmup 10 --no-cpu-baseline --angles 180
-  traffic angles180_compact python3 "$ROOT/bench.py" --steps 50 --warmup 10 --no-cpu-baseline --angles 180 --plan-format compact
-  traffic n512 python3 "$ROOT/bench.py" --no-cpu-baseline --mode n512
+  traffic bench python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline
+  traffic angles180 python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline --angles 180
+  traffic angles180_compact python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline --angles 180 --plan-format compact
+  traffic n512 python3 "$ROOT/bench.py" --full --no-cpu-baseline --mode n512
   traffic training_call python3 "$ROOT/tools/trace_training_call.py" 50
   ;;
 sq)

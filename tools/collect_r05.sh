@@ -20,7 +20,7 @@ traffic() { # traffic <name> <program + args...>: two PMC passes -> <name>_traff
   rocprofv3 --kernel-trace --pmc WRITE_SIZE -d /tmp/pmcw_$name -o w -- "$@" > "$OUT/$name.write.log" 2>&1
   python3 "$ROOT/tools/pmc_to_json.py" traffic "$(find /tmp/pmcf_$name -name '*.db' | head -1)" "$(find /tmp/pmcw_$name -name '*.db' | head -1)" > "$OUT/${name}_traffic_pmc.json"
 }
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 for part in $PARTS; do case $part in
 bench)
   $B > "$OUT/bench.json" 2> "$OUT/bench.err"
@@ -32,12 +32,12 @@ bench)
 stats)
   stats modes python3 "$ROOT/tools/time_modes.py" --shapes headline --n 200
   stats modes_n512 python3 "$ROOT/tools/time_modes.py" --shapes n512 --n 20
-  stats bench python3 "$ROOT/bench.py" --no-cpu-baseline --no-modes
-  stats moden512 python3 "$ROOT/bench.py" --no-cpu-baseline --mode n512
+  stats bench python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-modes
+  stats moden512 python3 "$ROOT/bench.py" --full --no-cpu-baseline --mode n512
   ;;
 traffic)
   traffic modes python3 "$ROOT/tools/time_modes.py" --shapes headline --n 50
-  traffic bench python3 "$ROOT/bench.py" --steps 50 --warmup 10 --no-cpu-baseline --no-modes
+  traffic bench python3 "$ROOT/bench.py" --full --steps 50 --warmup 10 --no-cpu-baseline --no-modes
   ;;
 scaling)
   $B --project-scaling --angles 180 --total-batch 400 > "$OUT/projected_scaling.json" 2>> "$OUT/bench.err"
