@@ -14,7 +14,8 @@
 //   rotate_tile_reduce_kernel     adds the tiles' partial sinograms in tile order (+ the log-likelihood epilogue);
 //   rotate_bwd_tfcompat_seg_kernel  direct NEAREST backward: an 80-bin cotangent segment per angle and pixel tile;
 //   rotate_bwd_tfcompat_fast_kernel bilinear backward (whole cotangent rows in LDS);
-//   rotate_fwd_kernel, rotate_bwd_tfcompat_kernel, rotate_bwd_exact_kernel   generic fallbacks, exact transpose.
+//   rotate_fwd_kernel, rotate_bwd_tfcompat_kernel, rotate_bwd_exact_kernel   generic fallbacks, exact transpose;
+//   rotate_bwd_f64_kernel         both backward modes of the float64 forward (rotate_fwd_kernel<double>), in double.
 // Every lane owns one ray (angle a, detector bin j) and walks canvas rows in ascending order -- the summation order of
 // reduce_sum(axis=1) as the CPU restatement fixes it -- or, tiled, the rows inside each tile and then the tiles in
 // order (oracle_rotate_fwd_tiled); results are reproducible bit for bit against the restatement either way.
@@ -1398,6 +1399,130 @@ __global__ __launch_bounds__(256) void rotate_bwd_exact_kernel(const float *__re
     }
 }
 
+// ---- backward of the float64 forward (rotate_fwd_kernel<double>): ctpvae_rotate_bwd_f64 ----------------------------------
+// Both modes in T = double, correctness-first (like the forward): every lane owns up to 8 pixels of one slice and walks the
+// angles in ascending order; the cotangent rows of a chunk of angles sit in LDS at 8 B per bin (the slice itself is never
+// staged, so 512 x 512 needs no separate path).  Coordinates and weights stay fp32 and unfused (-ffp-contract=off).
+//   TF_COMPAT: TensorFlow's gradient for T = double -- the cotangent row broadcast over the canvas rows, resampled with the
+//     inverted rows, summed over angles, cropped; the fp32 weights are promoted to double in the forward's expression order.
+//   EXACT: the transpose of ctpvae_rotate_fwd_f64 as a gather.  A sample (a, i, j) whose tap is this pixel lies within
+//     sqrt(2) of the pixel's inverse position, so the +-2 x +-2 window around it holds every such sample; each candidate's
+//     coordinates are recomputed with the forward's own fp32 expression (tap membership is the forward's, bit for bit) and its
+//     term is ((double)wy * (double)wx) * g -- the product of two fp32 weights is exact in double.  Terms are added in (angle,
+//     canvas row, bin) order: the per-pixel order of a scatter in (a, i, j) order.  No atomics, no plan, fixed bits.
+//     The window assumes rows that are rotations (what ctpvae_rotate_transforms_f32 builds).
+__device__ __forceinline__ double bcast_read64(const double *grow, int PH, int PW, int iy, int ix)
+{
+    return ((unsigned)iy < (unsigned)PH && (unsigned)ix < (unsigned)PW) ? grow[ix] : 0.0;
+}
+
+constexpr int kBwd64TabFloats = 16;   // per angle in LDS: the 8 rows as given, then (EXACT) the 6 inverse coefficients
+
+template <int INTERP, int MODE>
+__global__ __launch_bounds__(256) void rotate_bwd_f64_kernel(const double *__restrict__ gsino, RotGeom g,
+                                                             const float *__restrict__ T8, int chunk_a, int px_per_thread,
+                                                             double *__restrict__ gimg)
+{
+    extern __shared__ float lds_raw[];   // [chunk_a][PW] doubles, then [chunk_a][kBwd64TabFloats] floats
+    double *lds = reinterpret_cast<double *>(lds_raw);
+    float *lds_t = reinterpret_cast<float *>(lds + (size_t)chunk_a * g.PW);
+    const int s = blockIdx.y;
+    const int npix = g.H * g.W;
+    const int base = blockIdx.x * blockDim.x * px_per_thread;
+    constexpr int kMaxPpt = 8;
+    double acc[kMaxPpt];
+#pragma unroll
+    for (int k = 0; k < kMaxPpt; ++k) acc[k] = 0.0;
+
+    for (int ac = 0; ac < g.A; ac += chunk_a) {
+        const int na = min(chunk_a, g.A - ac);
+        __syncthreads();
+        const double *src = gsino + ((size_t)s * g.A + ac) * g.PW;
+        for (int p = threadIdx.x; p < na * g.PW; p += blockDim.x) lds[p] = src[p];
+        for (int al = threadIdx.x; al < na; al += blockDim.x) {
+            const float *t = T8 + (size_t)(ac + al) * 8;
+            float *d = lds_t + kBwd64TabFloats * al;
+            for (int k = 0; k < 8; ++k) d[k] = t[k];
+            if (MODE == CTPVAE_BWD_EXACT) {
+                // (j, i) of a canvas point (x, y): the inverse of the linear part, in double -- only a window centre
+                const double t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], t4 = t[4], t5 = t[5];
+                const double det = t0 * t4 - t1 * t3;
+                d[8] = (float)(t4 / det);
+                d[9] = (float)(-t1 / det);
+                d[10] = (float)((t1 * t5 - t4 * t2) / det);
+                d[11] = (float)(-t3 / det);
+                d[12] = (float)(t0 / det);
+                d[13] = (float)((t3 * t2 - t0 * t5) / det);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < kMaxPpt; ++k) {
+            if (k >= px_per_thread) break;
+            const int p = base + k * blockDim.x + threadIdx.x;
+            if (p >= npix) continue;
+            const int r = p / g.W, c = p - r * g.W;
+            const int X = c + g.px, Y = r + g.py;
+            const float fx = (float)X, fy = (float)Y;
+            double sum = acc[k];
+            for (int al = 0; al < na; ++al) {
+                const float *t = lds_t + kBwd64TabFloats * al;
+                const double *grow = lds + (size_t)al * g.PW;
+                if (MODE == CTPVAE_BWD_TF_COMPAT) {
+                    const float x = (t[0] * fx + t[1] * fy) + t[2];
+                    const float y = (t[3] * fx + t[4] * fy) + t[5];
+                    double v;
+                    if (INTERP == CTPVAE_NEAREST) {
+                        v = bcast_read64(grow, g.PH, g.PW, (int)round_half_away(y), (int)round_half_away(x));
+                    } else {
+                        const float yf = floorf(y), xf = floorf(x);
+                        const float yc = yf + 1.0f, xc = xf + 1.0f;
+                        const double v_yf = (double)(xc - x) * bcast_read64(grow, g.PH, g.PW, (int)yf, (int)xf) +
+                                            (double)(x - xf) * bcast_read64(grow, g.PH, g.PW, (int)yf, (int)xc);
+                        const double v_yc = (double)(xc - x) * bcast_read64(grow, g.PH, g.PW, (int)yc, (int)xf) +
+                                            (double)(x - xf) * bcast_read64(grow, g.PH, g.PW, (int)yc, (int)xc);
+                        v = (double)(yc - y) * v_yf + (double)(y - yf) * v_yc;
+                    }
+                    sum += v;
+                } else {
+                    const float j0 = (t[8] * fx + t[9] * fy) + t[10];
+                    const float i0 = (t[11] * fx + t[12] * fy) + t[13];
+                    int jc = 0, ic = 0;
+                    if (fabsf(j0) < 1.0e7f && fabsf(i0) < 1.0e7f) {
+                        jc = (int)round_half_away(j0);
+                        ic = (int)round_half_away(i0);
+                    }
+                    for (int i = max(ic - 2, 0); i <= min(ic + 2, g.PH - 1); ++i) {
+                        const float fi = (float)i;
+                        for (int j = max(jc - 2, 0); j <= min(jc + 2, g.PW - 1); ++j) {
+                            const float fj = (float)j;
+                            const float x = (t[0] * fj + t[1] * fi) + t[2];
+                            const float y = (t[3] * fj + t[4] * fi) + t[5];
+                            if (INTERP == CTPVAE_NEAREST) {
+                                if ((int)round_half_away(x) == X && (int)round_half_away(y) == Y) sum += grow[j];
+                            } else {
+                                const float yf = floorf(y), xf = floorf(x);
+                                const float yc = yf + 1.0f, xc = xf + 1.0f;
+                                float wx, wy;
+                                if ((int)xf == X) wx = xc - x; else if ((int)xc == X) wx = x - xf; else continue;
+                                if ((int)yf == Y) wy = yc - y; else if ((int)yc == Y) wy = y - yf; else continue;
+                                sum += ((double)wy * (double)wx) * grow[j];
+                            }
+                        }
+                    }
+                }
+            }
+            acc[k] = sum;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kMaxPpt; ++k) {
+        if (k >= px_per_thread) break;
+        const int p = base + k * blockDim.x + threadIdx.x;
+        if (p < npix) gimg[(size_t)s * npix + p] = acc[k];
+    }
+}
+
 static int check_geom(const char *who, int S, int H, int W, int PH, int PW, int py, int px, int A, int interp)
 {
     CTPVAE_REQUIRE(S > 0 && H > 0 && W > 0 && A > 0, "%s: sizes must be positive (S=%d H=%d W=%d A=%d)", who,
@@ -2008,6 +2133,40 @@ int ctpvae_rotate_fwd_f64(const double *img_dev, int S, int H, int W, int PH, in
                            : launch(rotate_fwd_kernel<double, CTPVAE_NEAREST, false>, 0);
         return use_lds ? launch(rotate_fwd_kernel<double, CTPVAE_BILINEAR, true>, lds_bytes)
                        : launch(rotate_fwd_kernel<double, CTPVAE_BILINEAR, false>, 0);
+    });
+}
+
+int ctpvae_rotate_bwd_f64(const double *gsino_dev, int S, int A, int PH, int PW, const float *T8_dev, int interp, int mode,
+                          int H, int W, int py, int px, double *gimg_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(gsino_dev && T8_dev && gimg_dev && S > 0 && H > 0 && W > 0 && A > 0 && PW > 0, "rotate_bwd_f64: null pointer or empty sizes");
+    if (int rc = check_geom("rotate_bwd_f64", 1, H, W, PH, PW, py, px, A, interp)) return rc;
+    CTPVAE_REQUIRE(mode == CTPVAE_BWD_TF_COMPAT || mode == CTPVAE_BWD_EXACT, "rotate_bwd_f64: unknown mode %d", mode);
+    // cotangent rows of a chunk of angles: <= 48 KiB per chunk, or one row alone when a row is larger than that
+    const size_t per_angle = (size_t)PW * sizeof(double) + kBwd64TabFloats * sizeof(float);
+    const int chunk_a = (int)std::min<size_t>((size_t)A, std::max<size_t>(1, (48 * 1024) / per_angle));
+    const size_t shmem = (size_t)chunk_a * per_angle;
+    CTPVAE_REQUIRE(shmem <= (size_t)kMaxLdsBytes, "rotate_bwd_f64: a detector row of %d bins does not fit LDS", PW);
+    const int npix = H * W;
+    return for_slice_chunks(S, max_slices_per_launch(), [&](int s0, int n) {
+        const RotGeom g{n, H, W, PH, PW, py, px, A};
+        int ppt = 8;
+        while (ppt > 1 && (long long)n * ceil_div(npix, 256 * ppt) < 512) ppt /= 2;
+        const dim3 grid(ceil_div(npix, 256 * ppt), n), block(256);
+        const double *gs = gsino_dev + (size_t)s0 * A * PW;
+        double *gi = gimg_dev + (size_t)s0 * npix;
+        auto launch = [&](auto kernel) -> int {
+            if (shmem > 64 * 1024)
+                CTPVAE_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+            hipLaunchKernelGGL(kernel, grid, block, shmem, (hipStream_t)stream, gs, g, T8_dev, chunk_a, ppt, gi);
+            CTPVAE_LAUNCH_CHECK("rotate_bwd_f64_kernel");
+            return CTPVAE_OK;
+        };
+        if (mode == CTPVAE_BWD_TF_COMPAT)
+            return interp == CTPVAE_NEAREST ? launch(rotate_bwd_f64_kernel<CTPVAE_NEAREST, CTPVAE_BWD_TF_COMPAT>)
+                                            : launch(rotate_bwd_f64_kernel<CTPVAE_BILINEAR, CTPVAE_BWD_TF_COMPAT>);
+        return interp == CTPVAE_NEAREST ? launch(rotate_bwd_f64_kernel<CTPVAE_NEAREST, CTPVAE_BWD_EXACT>)
+                                        : launch(rotate_bwd_f64_kernel<CTPVAE_BILINEAR, CTPVAE_BWD_EXACT>);
     });
 }
 

@@ -527,6 +527,33 @@ class RotatePlan:
                                                        _stream_ptr(self._dev_index)), "rotate_fwd_f64")
         return out
 
+    def backward_f64(self, gsino, out=None, angles_i=None):
+        """float64 cotangents [S][A][PW] -> float64 gradient images [S][H][W], the gradient of forward_f64 in double
+        (ctpvae_rotate_bwd_f64), in this plan's backward mode: "tf_compat" is TensorFlow's gradient for a float64 image (fp32
+        coordinates and weights, double taps, products and sums), "exact" the transpose of forward_f64 (weights wy * wx formed
+        in double).  Dense angles only: angles_i must be None."""
+        if angles_i is not None:
+            raise ValueError("backward_f64 takes the plan's dense angles only (angles_i must be None)")
+        if (gsino.dim() != 3 or tuple(gsino.shape[1:]) != (self.A, self.PW) or gsino.dtype is not torch.float64
+                or not gsino.is_contiguous() or gsino.device != self._tdev):
+            raise ValueError(f"gsino must be a contiguous float64 tensor [S][{self.A}][{self.PW}] on {self._tdev} "
+                             f"(got {tuple(gsino.shape)}, {gsino.dtype}, {gsino.device})")
+        S = gsino.shape[0]
+        if out is None:
+            out = _new_output((S, self.H, self.W), torch.float64, gsino.device)
+        elif (tuple(out.shape) != (S, self.H, self.W) or out.dtype is not torch.float64 or not out.is_contiguous()
+              or out.device != self._tdev):
+            raise ValueError(f"out must be a contiguous float64 tensor [{S}][{self.H}][{self.W}] on {self._tdev} "
+                             f"(got {tuple(out.shape)}, {out.dtype}, {out.device})")
+        if S == 0:
+            return out
+        tab = self.Tinv8 if self.mode == _lib.BWD_TF_COMPAT else self.T8
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._lib.ctpvae_rotate_bwd_f64(gsino.data_ptr(), S, self.A, self.PH, self.PW, tab.data_ptr(), self.interp,
+                                                       self.mode, self.H, self.W, self.py, self.px, out.data_ptr(),
+                                                       _stream_ptr(self._dev_index)), "rotate_bwd_f64")
+        return out
+
     def forward_loglik(self, img, mask, meas, pnm, eps, out=None, out_lp=None, out_dlp=None, with_dlp=False,
                        angles_i=None, dense_inputs=False):
         """Forward with the log-likelihood epilogue (one launch): returns (sino, lp), both [S][A][PW];
@@ -965,11 +992,14 @@ class _RotateProject(torch.autograd.Function):
             g = gout.permute(2, 0, 1)
         else:
             g = gout
-        if g.dtype is not torch.float32:
-            g = g.to(torch.float32)
-        if not g.is_contiguous():
-            g = g.contiguous()
-        gimg = plan.backward(g)              # [S][H][W]
+        if ctx.in_dtype is torch.float64:    # the gradient of forward_f64, in double
+            gimg = plan.backward_f64(g.to(torch.float64).contiguous())
+        else:
+            if g.dtype is not torch.float32:
+                g = g.to(torch.float32)
+            if not g.is_contiguous():
+                g = g.contiguous()
+            gimg = plan.backward(g)          # [S][H][W]
         if layout == _LAYOUT_VAE:
             gimg = gimg.unsqueeze(-1)
         elif layout == _LAYOUT_DIM3:
@@ -1141,6 +1171,10 @@ def project_tf_fast(phantom, theta, pad=False, dim=3, integrate_vae=False, *, in
     batch_size x angles x P x 1.  Every slice is rotated by -theta (nearest neighbour, zero fill) and summed
     over image rows.
 
+    dtype: the result has the phantom's dtype.  A float64 phantom is projected AND differentiated in float64 -- TensorFlow's
+    arithmetic for T = double: fp32 coordinates and weights, double taps, products and sums; its gradient is TensorFlow's for
+    T = double (backward="tf_compat") or the transpose of that forward (backward="exact").  Other dtypes run in float32.
+
     model="siddon" (keyword-only extension): the same layouts through TomoPy's ray-driven projector -- what
     the reference's data were MADE with (scripts/images_to_sinograms.py:62-66) -- differentiable through its exact
     transpose; `interp` and `backward` do not apply to it."""
@@ -1153,5 +1187,7 @@ def project_tf_fast(phantom, theta, pad=False, dim=3, integrate_vae=False, *, in
 
 def project_tf_low_mem(phantom, theta, pad=False, *, interp="bilinear", backward="tf_compat"):
     """Per-angle Radon forward, ctvae/forward_functions.py:49-78: img_size_x x img_size_y x img_size_z ->
-    angles x img_size_y x img_size_z, bilinear interpolation."""
+    angles x img_size_y x img_size_z, bilinear interpolation.  A float64 phantom is projected and differentiated in float64, as
+    in project_tf_fast (fp32 coordinates and weights, double sums; gradient: TensorFlow's for T = double, or the exact
+    transpose)."""
     return _project(phantom, theta, pad, 3, False, interp, backward)

@@ -21,6 +21,7 @@
  *   ctpvae_rotate_fwd_tiled_f32                the same operator for slices larger than LDS (config 5, 512 x 512)
  *   ctpvae_rotate_bwd_f32                      autodiff of the above (tf.GradientTape,
  *                                              ctvae/main_ct_vae.py:471-481) and its exact transpose
+ *   ctpvae_rotate_{fwd,bwd}_f64                the same pair on float64 images (ctvae/tomopy_forward_compare.py:52,56)
  *   ctpvae_rotate_plan_* / _planned_f32        the same two operators, batched: index arithmetic hoisted
  *                                              out of the per-object work (no counterpart in the reference)
  *   ctpvae_rotate_cplan_* / _fwd_compact_f32   the planned forward with step-coded (2 bits per sample) plans
@@ -115,6 +116,16 @@ int ctpvae_rotate_fwd_f32(const float *img_dev, int S, int H, int W, int PH, int
  * double; a correctness-first kernel (one ray per lane, the slice in LDS when 8 H (W + 1) bytes fit).  Round 5, ABI 3400. */
 int ctpvae_rotate_fwd_f64(const double *img_dev, int S, int H, int W, int PH, int PW, int py, int px,
                           const float *T8_dev, int A, int interp, double *sino_dev, ctpvae_stream_t stream);
+/* ... and its backward in double (round 6, ABI 3400: an added entry point).  Arguments and rows as ctpvae_rotate_bwd_f32
+ * (CTPVAE_BWD_TF_COMPAT takes the INVERTED rows, CTPVAE_BWD_EXACT the FORWARD rows); gsino / gimg are double.
+ * TF_COMPAT: TensorFlow's gradient for T = double -- fp32 coordinates and weights, double taps, products and sums, angles added
+ *   in ascending order.
+ * EXACT: the transpose of ctpvae_rotate_fwd_f64, gimg[s][r][c] = sum over angles, canvas rows, bins (in that order) of the
+ *   samples whose tap is (r, c) of ((double)wy * (double)wx) * gsino[s][a][j] (nearest: 1 * g), wy, wx the forward's own fp32
+ *   weights.  A deterministic gather (no atomics, no plan); the rows must be rotations, as ctpvae_rotate_transforms_f32 makes.
+ * Both: fixed bits, a correctness-first kernel (the cotangent rows of a chunk of angles in LDS, 8 B per bin). */
+int ctpvae_rotate_bwd_f64(const double *gsino_dev, int S, int A, int PH, int PW, const float *T8_dev, int interp, int mode,
+                          int H, int W, int py, int px, double *gimg_dev, ctpvae_stream_t stream);
 
 /* ---- a2 for slices larger than LDS (512 x 512): tiled forward, NEAREST -----------------------
  * The slice is cut into tiles 64 wide x tile_h tall, tile_h = ceil(H / ceil(H / 128)) (EQUAL rows of tiles, ABI 3310: 128 for
