@@ -266,15 +266,19 @@ class RotatePlan:
         if (use_plan and self.interp == _lib.NEAREST and self.mode == _lib.BWD_TF_COMPAT and self.py > 0 and self.px > 0
                 and self.A <= 65535 and self.H * self.W >= 128 * 128):
             self._step_plan = self._build_step_plan()
-        if self._want_exact_plan:
-            # built here, not on the first backward: reading its overflow word synchronises the stream, which must not
-            # happen inside a caller's HIP-graph capture
+        self._exact_bilin_plan = None
+        self._subsets = {}         # exact mode: subset plans per index vector (see subset)
+        if use_plan and self.mode == _lib.BWD_EXACT:
+            self._build_exact_plans()
+
+    def _build_exact_plans(self):
+        """The gather plans of the exact transpose.  Built at construction, not on the first backward: reading their overflow
+        words synchronises the stream, which must not happen inside a caller's HIP-graph capture."""
+        if self.interp == _lib.NEAREST:
             self._build_exact_plan()
         # exact transpose through an inverse plan of SUMMED WEIGHTS (round 5): the bilinear forward's at every size, the nearest
         # forward's where the byte plan above does not hold the geometry (512 x 512: the scatter there is 6 G global atomics)
-        self._exact_bilin_plan = None
-        if (use_plan and self.mode == _lib.BWD_EXACT and self.H <= 65535
-                and (self.interp == _lib.BILINEAR or self._exact_plan is None)):
+        if self.H <= 65535 and (self.interp == _lib.BILINEAR or self._exact_plan is None):
             self._build_exact_bilinear_plan()
 
     def _build_plan(self, which):
@@ -409,7 +413,10 @@ class RotatePlan:
         (ctpvae_loglik_object_sums_f32 / oracle.loglik_object_sums).  On a compact plan the reduction happens INSIDE the
         projector launch: neither the sinogram nor the log-probabilities are written to HBM, only dlp (the
         backward's operand) and one partial per (object, angle, 64-bin task).  Other planned / tiled geometries write the
-        log-probabilities and reduce them with the same-order kernel."""
+        log-probabilities and reduce them with the same-order kernel.  Nearest plans only, like forward_loglik: the tiled
+        kernel below has no bilinear form, and its workspace would be the (smaller) bilinear one."""
+        if self.interp != _lib.NEAREST:
+            raise ValueError("forward_loglik needs a planned or tiled forward (nearest)")
         if angles_i is not None and not self.sel_supported(angles_i.numel()):
             if dense_inputs:
                 idx = self._sel_dev(angles_i).long()
@@ -480,13 +487,38 @@ class RotatePlan:
         """The subset as a device vector (kernels without a host-index form; torch gathers)."""
         return angles_i if angles_i.device == self._tdev else angles_i.to(self._tdev)
 
+    SUBSET_CACHE_MAX = 4
+
     def subset(self, angles_i):
-        """A plan over rows `angles_i` of this one's tables (two small gathers, no plan kernels): the fallback for angle
-        subsets on paths whose kernels take no angle-index operand (tiled / bilinear forward, exact backward)."""
+        """A plan over rows `angles_i` of this one's tables (two small gathers): the fallback for angle subsets on paths whose
+        kernels take no angle-index operand (tiled / bilinear forward, exact backward).  Its forward is unplanned where this
+        plan's forward is planned.  Its exact backward is the deterministic gather a plan built for those rows runs, whatever
+        was called on this plan before (not the scatter kernel, whose atomics fix no order).  The gather plans cost a build
+        and a synchronisation, so exact subsets are kept per index vector -- a host one by value, a device one by object and
+        in-place version (like a device theta in _cached_plan): a training loop that reuses its subset builds once."""
+        key = self._subset_key(angles_i) if self.mode == _lib.BWD_EXACT else None
+        hit = self._subsets.get(key) if key is not None else None
+        if hit is not None and (hit[0] is None or hit[0]() is angles_i):
+            return hit[1]
         idx = as_angle_index(angles_i, self._tdev).long()
-        return RotatePlan(None, self.H, self.W, self._pad, self.device, interp=self._interp_name,
-                          backward=self._backward_name, use_plan=False if self._fwd_plan is not None else self._use_tiles,
-                          _tables=(self.T8.index_select(0, idx), self.Tinv8.index_select(0, idx)))
+        use_plan = False if self._fwd_plan is not None else self._use_tiles
+        sub = RotatePlan(None, self.H, self.W, self._pad, self.device, interp=self._interp_name, backward=self._backward_name,
+                         use_plan=use_plan, _tables=(self.T8.index_select(0, idx), self.Tinv8.index_select(0, idx)))
+        if key is not None:
+            if not use_plan:
+                sub._build_exact_plans()
+            if len(self._subsets) >= self.SUBSET_CACHE_MAX:
+                self._subsets.pop(next(iter(self._subsets)))
+            dev_ref = weakref.ref(angles_i) if key[0] == "dev" else None
+            self._subsets[key] = (dev_ref, sub)
+        return sub
+
+    @staticmethod
+    def _subset_key(angles_i):
+        if isinstance(angles_i, torch.Tensor) and angles_i.device.type != "cpu":
+            return ("dev", id(angles_i), angles_i._version, angles_i.data_ptr(), tuple(angles_i.shape), angles_i.dtype)
+        host = as_angle_index(angles_i, None, keep_host=True)
+        return ("host", host.numpy().tobytes())
 
     def sel_supported(self, n, forward=True):
         """True if a launch over `n` selected angles runs on THIS (dense) plan with an angle-index operand."""
@@ -563,6 +595,8 @@ class RotatePlan:
         angles_i (planned geometries): int32 device vector of plan angles; outputs are [S][len(angles_i)][PW].  With
         dense_inputs, mask [S][A] and meas [S][A][PW] are the DENSE arrays and the kernel reads them at the selected
         angles (the reference's tf.gather of both, ctvae/helper_functions.py:356-357, costs no launch)."""
+        if self.interp != _lib.NEAREST:        # before a subset plan is built for nothing
+            raise ValueError("forward_loglik needs a planned or tiled forward (nearest)")
         if angles_i is not None and not self.sel_supported(angles_i.numel()):
             if dense_inputs:
                 idx = self._sel_dev(angles_i).long()
@@ -578,6 +612,8 @@ class RotatePlan:
         scale: optional float32 device tensor of S per-slice factors (any stride, 0 included: an expanded scalar)
         applied in the kernel's store -- nearest / tf_compat only (`supports_scale`).
         angles_i: the cotangents are [S][len(angles_i)][PW], row k belonging to plan angle angles_i[k]."""
+        if scale is not None and not self.supports_scale:     # before a subset plan is built for nothing
+            raise ValueError("a per-slice scale needs interp='nearest' and backward='tf_compat'")
         n = self.A if angles_i is None else angles_i.numel()
         if gsino.dim() == 3 and gsino.shape[0] == 0 and tuple(gsino.shape[1:]) == (n, self.PW):
             return out if out is not None else gsino.new_empty((0, self.H, self.W))
@@ -618,7 +654,7 @@ class RotatePlan:
 
     @property
     def tiled(self):
-        """True if the forward cuts slices into LDS-sized tiles (slices larger than LDS, nearest)."""
+        """True if the forward cuts slices into LDS-sized tiles (slices larger than LDS, nearest and bilinear)."""
         return self._tile_workspace(1) is not None
 
     def _check_sel(self, angles_i):

@@ -1091,8 +1091,14 @@ def test_angle_subsets_on_geometries_without_an_index_operand(oracle):
         if code:
             np.testing.assert_array_equal(got, oracle.rotate_fwd(small, geo40, T40[sub], code))
         g40 = rng.standard_normal((2, 7, plan.PW)).astype(np.float32)
-        gb = to_np(plan.backward(torch.from_numpy(g40).to(d), angles_i=idx))
+        gb_t = plan.backward(torch.from_numpy(g40).to(d), angles_i=idx)
+        gb = to_np(gb_t)
         assert rel_err(gb, ref_b(g40, T40[sub])) <= REL
+        if not code:       # exact: the very gather of a plan built for the gathered rows, bit for bit
+            rows = idx.long()
+            fresh = RotatePlan(None, 40, 40, True, d, backward="exact",
+                               _tables=(plan.T8.index_select(0, rows), plan.Tinv8.index_select(0, rows)))
+            assert torch.equal(gb_t, fresh.backward(torch.from_numpy(g40).to(d)))
     # the training call on the tiled geometry
     mask = torch.from_numpy(((rng.random((3, A)) > 0.3) / 7).astype(np.float32)).to(d)
     meas = torch.from_numpy((rng.random((3, A, big.PW)) * 3).astype(np.float32)).to(d)
