@@ -240,6 +240,84 @@ __device__ __forceinline__ void stage_unit_pow2(float *lds, const float *const (
     else stage_unit_pow2_m<NS, NB, false>(lds, src, rows, cs, src_stride, pitch, lane, wave, nwaves, between);
 }
 
+// R rows that lie back to back in memory (row stride == cols: a slice's cotangent rows, 184 or 728 bins -- no power of two, so not for
+// stage_unit_pow2), cols % 4 == 0, 16-byte aligned bases, NS slices interleaved.  The lean form of stage_rows_interleaved_v4 for the
+// launches whose prologue is most of their time (the planned backward at few angles): a 16-lane group takes a unit of 4 rows x 4
+// float4 -- lane = (row k = (lane >> 2) & 3, float4 m = lane & 3) -- so that the sixteen cells a ds_write_b64 lane group (16 contiguous
+// lanes, 32 banks = 16 cells of two slices) writes are (row + 4 m + e) mod 16 with pitch == 1 (mod 16): all distinct.  (A flat float4
+// index per lane would put 16 lanes in ONE row, 4 cells apart: 4-way conflicts on every store.)  Unit U = group + i * groups ->
+// (row quad, unit in the quad) by ONE multiplication with the host's word contig_rows_magic(cols) (U < 2^9, no division, no
+// carried (rq, pc) pair); all loads of a batch (NB units per lane) are issued back to back, between() runs while they fly, then the writes.
+// Whole units past the block are skipped wave-uniformly; a lane past a ragged edge loads float4 0 of the block and writes nothing.
+__host__ __device__ inline int contig_rows_units_per_quad(int cols) { return (cols + 15) >> 4; }
+__host__ __device__ inline unsigned contig_rows_magic(int cols) { return 65536u / (unsigned)contig_rows_units_per_quad(cols) + 1u; }
+// units u0 + i * groups + group, i < NB: one batch (contig_rows_units(): all units of the block)
+__host__ __device__ inline int contig_rows_units(int rows, int cols) { return ((rows + 3) >> 2) * contig_rows_units_per_quad(cols); }
+template <int NS, int NB, class F>
+__device__ __forceinline__ void stage_contig_rows_batch(float *lds, const float *const (&src)[NS], int rows, int cols, int pitch,
+                                                        unsigned magic, int tid, int nthreads, int u0, F between)
+{
+    typedef float vec_t __attribute__((ext_vector_type(NS)));
+    const unsigned c4 = (unsigned)cols >> 2, upr = (unsigned)contig_rows_units_per_quad(cols);
+    const int nunits = contig_rows_units(rows, cols), ngroups = nthreads >> 4;
+    const unsigned grp = (unsigned)tid >> 4, k = ((unsigned)tid >> 2) & 3u, m = (unsigned)tid & 3u;
+    // (all operands are below 2^24 and so are the products: 24-bit multiplications, full rate; byte offsets are unsigned 32-bit, so
+    // that a load is an SGPR base plus one VGPR)
+    float4 v[NB][NS];
+    int cell[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        if (u0 + i * ngroups >= nunits) continue;                       // workgroup-uniform
+        const unsigned U = (unsigned)(u0 + i * ngroups) + grp;
+        const unsigned rq = __umul24(U, magic) >> 16, uc = U - __umul24(rq, upr);   // exact: U * upr < 2^16
+        const unsigned row = 4u * rq + k, col4 = 4u * uc + m;
+        const bool ok = row < (unsigned)rows && col4 < c4;
+        const unsigned off = ok ? (__umul24(row, c4) + col4) << 4 : 0u;
+        cell[i] = ok ? (int)(__umul24(row, (unsigned)pitch) + 4u * col4) : -1;
+#pragma unroll
+        for (int n = 0; n < NS; ++n) v[i][n] = *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(src[n]) + off);
+    }
+    between();
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        if (u0 + i * ngroups >= nunits || cell[i] < 0) continue;
+        vec_t *d = reinterpret_cast<vec_t *>(lds) + cell[i];
+        vec_t w0, w1, w2, w3;
+#pragma unroll
+        for (int n = 0; n < NS; ++n) {
+            w0[n] = v[i][n].x;
+            w1[n] = v[i][n].y;
+            w2[n] = v[i][n].z;
+            w3[n] = v[i][n].w;
+        }
+        d[0] = w0;
+        d[1] = w1;
+        d[2] = w2;
+        d[3] = w3;
+    }
+}
+// The first batch is straight-line code: in a loop its loads would wait for every load in flight before them (the kernel's index
+// vectors), because the loop reuses their registers.  A workgroup that is small for its block (contig_rows_more()) stages the rest in
+// a loop, which its kernel may well put behind the barrier that the one-batch launches run into.
+template <int NS, int NB, class F>
+__device__ __forceinline__ void stage_contig_rows(float *lds, const float *const (&src)[NS], int rows, int cols, int pitch, unsigned magic,
+                                                  int tid, int nthreads, F between)
+{
+    stage_contig_rows_batch<NS, NB>(lds, src, rows, cols, pitch, magic, tid, nthreads, 0, between);
+}
+template <int NB> __device__ __forceinline__ bool contig_rows_more(int rows, int cols, int nthreads)
+{
+    return contig_rows_units(rows, cols) > NB * (nthreads >> 4);
+}
+template <int NS, int NB>
+__device__ __forceinline__ void stage_contig_rows_rest(float *lds, const float *const (&src)[NS], int rows, int cols, int pitch,
+                                                       unsigned magic, int tid, int nthreads)
+{
+    const int step = NB * (nthreads >> 4);
+    for (int u0 = step; u0 < contig_rows_units(rows, cols); u0 += step)
+        stage_contig_rows_batch<NS, NB>(lds, src, rows, cols, pitch, magic, tid, nthreads, u0, [] {});
+}
+
 // log2 of a unit's 64-column blocks per row if the lean form serves it (wave-uniform), else -1
 __device__ __forceinline__ int unit_pow2_cs(int rows, int cols, int src_stride, int nwaves, int nb)
 {
@@ -279,7 +357,8 @@ __device__ __forceinline__ void stage_rows_interleaved(float *lds, const float *
 // A UNIT (a slice, a slice pair / quad, a tile) into LDS: the lean form where its shape allows (64 / 128 / 256 columns, rows in
 // fours, one batch of loads per lane, aligned rows), the general forms above otherwise.  For the forward kernels, whose units are
 // square slices and 64-column tiles; kernels that stage detector rows (184 or 728 bins) call the general forms directly -- with
-// the lean form compiled in beside them the planned backward ran 4 % slower (a longer prologue, another register allocation).
+// the lean form compiled in beside them the planned backward ran 4 % slower (a longer prologue, another register allocation) --,
+// and the planned backward's few-angle form has stage_contig_rows for them.
 template <int NS>
 __device__ __forceinline__ void stage_unit(float *lds, const float *const (&src)[NS], int rows, int cols, int src_stride, int pitch,
                                            bool mirror, int lane, int wave, int nwaves)

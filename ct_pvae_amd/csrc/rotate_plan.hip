@@ -327,6 +327,14 @@ __device__ __forceinline__ void gather8(const float *lds, const uint4 q, float (
 // (d = 1 has no 32-bit word -- and needs none: word 0 = "x itself"; d = 0 is never divided by)
 __host__ __device__ inline unsigned div_magic(unsigned d) { return d > 1 ? (unsigned)((1ull << 32) / d) + 1u : 0u; }
 __host__ __device__ inline unsigned div_by_magic(unsigned x, unsigned magic) { return magic ? (unsigned)(((unsigned long long)x * magic) >> 32) : x; }
+// x / d for EVERY 32-bit x: with the word floor(2^32 / d) the product's high half is the quotient or one below it (x m / 2^32 > x / d - 1),
+// and one compare mends it -- no operand is "too large", so a kernel that divides this way carries no division to fall back on
+__host__ __device__ inline unsigned div_magic_floor(unsigned d) { return d > 1 ? (unsigned)((1ull << 32) / d) : 0xffffffffu; }
+__host__ __device__ inline unsigned div_by_magic_floor(unsigned x, unsigned magic, unsigned d)
+{
+    const unsigned q = (unsigned)(((unsigned long long)x * magic) >> 32);
+    return q + (x - q * d >= d ? 1u : 0u);
+}
 
 // clist[c] = (count, the angles of class c in ascending order): the planned kernels' task lists; behind the two lists the
 // division words of the two counts (div_magic)
@@ -706,23 +714,41 @@ __device__ __forceinline__ void gather8(const float *lds, unsigned w0, unsigned 
 // kernel with twice the index vectors per staged row; sums are added in virtual-angle order = the scatter's order.
 // SHORT (at most 32 angles, DUP = 1: one staged chunk, two groups of sixteen): the second group's index vectors are requested at
 // the start with the first's -- loaded after the first group's gathers they put an L2 round trip behind the barrier of a launch
-// that is a few microseconds long -- and the chunk pipeline's registers make room for them.
+// that is a few microseconds long -- and the chunk pipeline's registers make room for them.  Such a launch is mostly prologue
+// (profiles/r05_rounds.txt, r07_bwd_headline_before.txt: 1.7 .. 2.7 of 4.7 us from a workgroup's start to its barrier, the more the more
+// waves share a SIMD), so the SHORT form is written for few instructions ahead of the barrier: its one chunk's bookkeeping is launch
+// constants, its block number is decoded with the mended multiplications of div_by_magic_floor (inv_tiles, inv_nxb are then
+// div_magic_floor words: no division behind them, knob NO_MAGIC does not apply), the wave number is a scalar, and the cotangent rows go
+// through stage_contig_rows (stage_magic != 0: the host found PW % 4 == 0 and a 16-byte aligned tensor) with the dead taps' zero cells
+// written while the loads fly; otherwise through the general stagers.
 template <int PPT, int MAXT, int NS, int DUP = 1, bool SHORT = false>
 __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *__restrict__ gsino, PlanGeom g, BwdLayout L,
                                                                  const uint4 *__restrict__ idx, int tiles_y, int g_S,
                                                                  SliceScale scale, float *__restrict__ gimg, unsigned inv_tiles,
-                                                                 unsigned inv_nxb)
+                                                                 unsigned inv_nxb, unsigned stage_magic)
 {
+    static_assert(!SHORT || DUP == 1, "SHORT launches are tf_compat plans of at most 32 angles");
     typedef typename SliceVec<NS>::type vec_t;
     constexpr int kChunk = kBwdChunk / NS;
     extern __shared__ float lds[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+    const int wave = SHORT ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
     const int tiles = L.nXB * tiles_y;
     const int units = (g_S + NS - 1) / NS;
     // Workgroups b and b + 8 share an XCD (round-robin dispatch; speed only): the tiles of one slice (pair) are placed
     // on one XCD so that its cotangent rows are fetched into one L2 -- block = (u / 8) * 8 * tiles + tile * 8 + u % 8.
     int u, tile;
-    {
+    if constexpr (SHORT) {
+        const unsigned per8 = 8u * tiles, octet = div_by_magic_floor(blockIdx.x >> 3, inv_tiles, tiles), rem = blockIdx.x - octet * per8;
+        if ((int)(octet + 1) * 8 <= units) {
+            tile = rem >> 3;
+            u = octet * 8 + (rem & 7);
+        } else {
+            const unsigned ru = div_by_magic_floor(rem, inv_tiles, tiles);
+            u = octet * 8 + ru;
+            tile = rem - ru * tiles;
+        }
+    } else {
         // (divisions by multiplication, div_magic: inv_tiles == 0 -- the host's "operands too large" -- divides)
         const int per8 = 8 * tiles;
         const int octet = inv_tiles ? (int)div_by_magic(blockIdx.x >> 3, inv_tiles) : (int)blockIdx.x / per8, rem = blockIdx.x - octet * per8;
@@ -738,9 +764,16 @@ __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *_
     const int s = u * NS;
     const bool has2 = NS == 2 && s + 1 < g_S;   // an odd batch ends with a half-empty pair (slice s staged twice)
     CTPVAE_PSTAMP(0);
-    const float k0 = scale.at(s), k1 = has2 ? scale.at(s + 1) : 1.0f;
-    const int ty = inv_tiles ? (int)div_by_magic((unsigned)tile, inv_nxb) : tile / L.nXB, xb = tile - ty * L.nXB;
-    const float *gs = gsino + (size_t)s * g.A * g.PW;
+    // (the per-slice factors are wanted at the very end: a SHORT launch asks for them behind its barrier)
+    float k0 = 1.0f, k1 = 1.0f;
+    if constexpr (!SHORT) k0 = scale.at(s), k1 = has2 ? scale.at(s + 1) : 1.0f;
+    const int ty = SHORT ? (int)div_by_magic_floor((unsigned)tile, inv_nxb, (unsigned)L.nXB)
+                         : (inv_tiles ? (int)div_by_magic((unsigned)tile, inv_nxb) : tile / L.nXB),
+              xb = tile - ty * L.nXB;
+    // (SHORT: at most 32 x 255 cotangents per slice, and a plan of two index groups: 2 H Wpad < 2^32 vectors with check_plan_geom's
+    // PH PW < 2^24 -- unsigned 32-bit products)
+    const size_t slice_elems = SHORT ? (size_t)(unsigned)(g.A * g.PW) : (size_t)g.A * g.PW;
+    const float *gs = SHORT ? gsino + (size_t)s * slice_elems : gsino + (size_t)s * g.A * g.PW;
     const int xcol = xb * 64 + lane;
     const int y0 = ty * (nwaves * PPT) + wave;   // this wave's rows: y0, y0 + nwaves, ...
     vec_t acc[PPT];
@@ -759,7 +792,7 @@ __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *_
 #ifdef CTPVAE_TUNE_BWD_NOIDX
             if (a16 > 0) continue;   // timing only: every group reuses the first index vectors (no index streaming)
 #endif
-            q[SLOT][k] = p[((size_t)a16 * g.H + y) * L.Wpad];
+            q[SLOT][k] = SHORT ? p[(unsigned)(a16 * g.H + y) * (unsigned)L.Wpad] : p[((size_t)a16 * g.H + y) * L.Wpad];
         }
     };
     load_group(0, std::integral_constant<int, 0>{});       // index loads fly while the cotangent rows land
@@ -768,7 +801,7 @@ __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *_
     if constexpr (SHORT) {
 #pragma unroll
         for (int k = 0; k < PPT; ++k)
-            q2nd[k] = p[((size_t)min(1, L.NA16 - 1) * g.H + min(y0 + k * nwaves, g.H - 1)) * L.Wpad];   // (its second group)
+            q2nd[k] = p[(unsigned)(min(1, L.NA16 - 1) * g.H + min(y0 + k * nwaves, g.H - 1)) * (unsigned)L.Wpad];   // (its second group)
     }
 
     const int VA = g.A * DUP;                            // virtual angles (= angles unless DUP = 2)
@@ -782,25 +815,41 @@ __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *_
     bool ahead_valid = false;
     auto chunk_srcs = [&](int ac, const float *(&srcs)[NS]) {
         srcs[0] = gs + (size_t)ac * g.PW;
-        if constexpr (NS == 2) srcs[1] = gs + (has2 ? (size_t)g.A * g.PW : 0) + (size_t)ac * g.PW;
+        if constexpr (NS == 2) srcs[1] = gs + (has2 ? slice_elems : 0) + (size_t)ac * g.PW;
     };
-    for (int acv = 0; acv < VA; acv += chunk) {
-        const int nav = min(chunk, VA - acv);
+    // (SHORT: the loop is its one trip with acv = 0 -- written so that the compiler sees it)
+    for (int acv = 0; acv < (SHORT ? 1 : VA); acv += (SHORT ? 1 : chunk)) {
+        const int nav = SHORT ? VA : min(chunk, VA - acv);
         const int na4 = (nav + 3) & ~3;             // taps are consumed a dword (4 virtual angles) at a time
         const int ac = acv / DUP;                   // first staged (real) angle of the chunk
         const int na = (nav + DUP - 1) / DUP;       // staged rows
         const int na_z = (na4 + DUP - 1) / DUP;     // rows a tap of this chunk may name
         if (acv > 0) __syncthreads();
         // a dead tap is byte 255: only cell 255 of every row (never a bin: PW <= 255) must hold 0.0f
-        for (int t = threadIdx.x; t < na_z * NS; t += blockDim.x) lds[((t / NS) * kBwdPitch + 255) * NS + (t % NS)] = 0.0f;
-        if (ahead_valid) {
-            ahead.commit(lds, kBwdPitch);           // requested during the previous chunk's gathers
-        } else if constexpr (NS == 1) {
-            stage_rows(lds, gs + (size_t)ac * g.PW, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
+        auto stage_general = [&] {
+            if constexpr (NS == 1) {
+                stage_rows(lds, gs + (size_t)ac * g.PW, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
+            } else {
+                const float *srcs[NS];
+                chunk_srcs(ac, srcs);
+                stage_rows_interleaved<2>(lds, srcs, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
+            }
+        };
+        if constexpr (SHORT) {   // (na_z <= 32 rows: one store of the first lanes, issued while the rows are in flight)
+            auto zero_cells = [&] {
+                if ((int)threadIdx.x < na_z) reinterpret_cast<vec_t *>(lds)[threadIdx.x * kBwdPitch + 255] = 0.0f;
+            };
+            if (stage_magic != 0) {   // launch-uniform
+                const float *srcs[NS];
+                chunk_srcs(0, srcs);
+                stage_contig_rows<NS, 8 / NS>(lds, srcs, na, g.PW, kBwdPitch, stage_magic, threadIdx.x, blockDim.x, zero_cells);
+            } else {
+                zero_cells();
+            }
         } else {
-            const float *srcs[NS];
-            chunk_srcs(ac, srcs);
-            stage_rows_interleaved<2>(lds, srcs, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
+            for (int t = threadIdx.x; t < na_z * NS; t += blockDim.x) lds[((t / NS) * kBwdPitch + 255) * NS + (t % NS)] = 0.0f;
+            if (ahead_valid) ahead.commit(lds, kBwdPitch);           // requested during the previous chunk's gathers
+            else stage_general();
         }
         ahead_valid = false;
         if (kPipe && acv + chunk < VA) {            // wave-uniform
@@ -814,6 +863,23 @@ __global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *_
         }
         if (acv == 0) CTPVAE_PSTAMP(1);
         __syncthreads();
+        if constexpr (SHORT) {
+            k0 = scale.at(s), k1 = has2 ? scale.at(s + 1) : 1.0f;
+            // Rows that stage_contig_rows cannot take (PW % 4 != 0, an unaligned tensor) go through the general stagers, and what a
+            // workgroup that is small for its rows could not request in one batch follows, BEHIND the barrier: the launches this form is
+            // written for run straight into their barrier and jump over this block.
+            const bool more = stage_magic != 0 && contig_rows_more<8 / NS>(na, g.PW, blockDim.x);
+            if (stage_magic == 0 || more) {   // launch-uniform
+                if (more) {
+                    const float *srcs[NS];
+                    chunk_srcs(0, srcs);
+                    stage_contig_rows_rest<NS, 8 / NS>(lds, srcs, na, g.PW, kBwdPitch, stage_magic, threadIdx.x, blockDim.x);
+                } else {
+                    stage_general();
+                }
+                __syncthreads();
+            }
+        }
         if (acv == 0) CTPVAE_PSTAMP(2);
         // up to four (eight with DUP = 2) groups of sixteen virtual angles, unrolled so that every row offset is an immediate
         auto group = [&](auto al_tag) {
@@ -1467,13 +1533,19 @@ static int launch_bwd_planned(const float *gsino_dev, int S, int H, int W, int P
     // (block numbers / 8 by the tiles per unit, by multiplication: exact while (nblk / 8) * tiles < 2^32; a unit of ONE tile
     // divides as before: its word would be 0, which the kernel reads as "divide")
     const bool small = (nblk / 8) * (long long)(L.nXB * tiles_y) < (1ll << 32) && L.nXB * tiles_y > 1 && knob(kKnobNoMagic) <= 0;
+    // SHORT launches (tf_compat, at most 32 angles) divide by mended multiplications whatever the operands, and stage cotangent rows
+    // that allow it (whole float4s, a 16-byte aligned tensor: then every slice's rows are aligned) with stage_contig_rows
+    const bool is_short = dup == 1 && A <= 32;
+    const unsigned inv_tiles = is_short ? div_magic_floor((unsigned)(L.nXB * tiles_y)) : (small ? div_magic((unsigned)(L.nXB * tiles_y)) : 0u);
+    const unsigned inv_nxb = is_short ? div_magic_floor((unsigned)L.nXB) : div_magic((unsigned)L.nXB);
+    const unsigned stage_magic = is_short && PW % 4 == 0 && (reinterpret_cast<uintptr_t>(gsino_dev) & 15) == 0 ? contig_rows_magic(PW) : 0u;
     auto launch = [&](auto kernel) -> int {
         static std::atomic<unsigned long long> attr_set{0}, abs_ok{0};   // per kernel instantiation: devices done
         CTPVAE_REQUIRE_NO_STATIC_LDS(kernel, "rotate_bwd_planned_kernel", abs_ok);
         CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
         hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(64 * waves), shmem, (hipStream_t)stream, gsino_dev, g, L,
                            (const uint4 *)bwd_plan_dev, tiles_y, S, SliceScale{scale_dev, scale_stride}, gimg_dev,
-                           small ? div_magic((unsigned)(L.nXB * tiles_y)) : 0u, div_magic((unsigned)L.nXB));
+                           inv_tiles, inv_nxb, stage_magic);
         return CTPVAE_OK;
     };
     int rc;
@@ -1482,7 +1554,7 @@ static int launch_bwd_planned(const float *gsino_dev, int S, int H, int W, int P
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<2, 256, 2, 2>) : launch(rotate_bwd_planned_kernel<2, 1024, 2, 2>);
         else
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<4, 256, 1, 2>) : launch(rotate_bwd_planned_kernel<4, 1024, 1, 2>);
-    } else if (A <= 32) {   // two index groups at most: both requested up front
+    } else if (is_short) {   // two index groups at most: both requested up front
         if (ns == 2)
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<2, 256, 2, 1, true>) : launch(rotate_bwd_planned_kernel<2, 1024, 2, 1, true>);
         else
