@@ -59,6 +59,9 @@ SIGNATURES = {
                                              _vp, _vp]),
     "ctpvae_rotate_fwd_tiled_interp_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _c_int,
                                                     _vp, _vp, _vp]),
+    "ctpvae_rotate_fwd_fast_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
+    "ctpvae_rotate_fwd_tiled_fast_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp,
+                                                  _vp, _vp]),
     "ctpvae_rotate_fwd_tiled_loglik_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _c_int,
                                                     _vp, _vp, _vp, _vp, _c_float, _vp, _vp, _vp, _vp]),
     "ctpvae_rotate_tplan_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int, _c_int]),

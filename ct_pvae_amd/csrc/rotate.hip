@@ -2180,6 +2180,21 @@ int ctpvae_rotate_fwd_f32(const float *img_dev, int S, int H, int W, int PH, int
     });
 }
 
+// precision "fast": the bilinear forward with the lerp / FMA blend (rotate_bilin.hip, FAST).  Every form of the bilinear kernel has its
+// fast twin; a call the bilinear kernel does not take is refused, never handed to an exact kernel -- but under the NO_PLAN /
+// FORCE_GENERIC knobs, which ask for round 1's direct kernels by name: those have no fast form and run as they are.
+int ctpvae_rotate_fwd_fast_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px,
+                               const float *T8_dev, int A, float *sino_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(img_dev && T8_dev && sino_dev && S > 0 && H > 0 && W > 0 && A > 0 && PW > 0, "rotate_fwd_fast: null pointer or empty sizes");
+    if (int rc = check_geom("rotate_fwd_fast", 1, H, W, PH, PW, py, px, A, CTPVAE_BILINEAR)) return rc;
+    if (knob(kKnobForceGeneric) >= 0 || knob(kKnobNoPlan) >= 0)
+        return ctpvae_rotate_fwd_f32(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, CTPVAE_BILINEAR, sino_dev, stream);
+    CTPVAE_REQUIRE(bilin_fwd_whole_ok(H, W, A), "rotate_fwd_fast: a %dx%d slice with the tables of %d angles does not fit LDS whole: no fast "
+                   "form (larger slices: ctpvae_rotate_fwd_tiled_fast_f32; thousands of angles: the exact ctpvae_rotate_fwd_f32)", H, W, A);
+    return bilin_fwd_whole(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, sino_dev, stream, true);
+}
+
 int ctpvae_rotate_tile_shape(int H, int W, int interp, int *tile_h, int *tile_w)
 {
     if (H <= 0 || W <= 0 || !tile_h || !tile_w) return fail(CTPVAE_EINVAL, "rotate_tile_shape: bad sizes / null pointer");
@@ -2313,11 +2328,28 @@ int ctpvae_rotate_fwd_tiled_f32(const float *img_dev, int S, int H, int W, int P
     return launch_fwd_tiled(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, workspace_dev, sino_dev, LogLikEpilogue{}, stream);
 }
 
+static int rotate_fwd_tiled_bilin(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev,
+                                  int A, int interp, void *workspace_dev, float *sino_dev, ctpvae_stream_t stream, bool fast);
+
 int ctpvae_rotate_fwd_tiled_interp_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev,
                                        int A, int interp, void *workspace_dev, float *sino_dev, ctpvae_stream_t stream)
 {
     if (interp == CTPVAE_NEAREST)
         return ctpvae_rotate_fwd_tiled_f32(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, workspace_dev, sino_dev, stream);
+    return rotate_fwd_tiled_bilin(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, interp, workspace_dev, sino_dev, stream, false);
+}
+
+// precision "fast": the tile kernel's fast twin, the same workspace, tile shape and reduce pass (the tiles' partial sums are added in
+// tile order, as for the exact kernel)
+int ctpvae_rotate_fwd_tiled_fast_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev,
+                                     int A, void *workspace_dev, float *sino_dev, ctpvae_stream_t stream)
+{
+    return rotate_fwd_tiled_bilin(img_dev, S, H, W, PH, PW, py, px, T8_dev, A, CTPVAE_BILINEAR, workspace_dev, sino_dev, stream, true);
+}
+
+static int rotate_fwd_tiled_bilin(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev,
+                                  int A, int interp, void *workspace_dev, float *sino_dev, ctpvae_stream_t stream, bool fast)
+{
     CTPVAE_REQUIRE(img_dev && T8_dev && workspace_dev && sino_dev && S > 0 && H > 0 && W > 0 && A > 0 && PW > 0,
                    "rotate_fwd_tiled: null pointer or empty sizes");
     if (int rc = check_geom("rotate_fwd_tiled", 1, H, W, PH, PW, py, px, A, interp)) return rc;
@@ -2329,7 +2361,7 @@ int ctpvae_rotate_fwd_tiled_interp_f32(const float *img_dev, int S, int H, int W
     const int nt = ts.ntx * ts.nty;
     const int chunk = std::max(4, std::min(max_slices_per_launch(), 65535 / nt) / 4 * 4);
     return for_slice_chunks(S, chunk, [&](int s0, int n) {
-        if (int rc = bilin_fwd_tiles(img_dev + (size_t)s0 * H * W, n, H, W, PH, PW, py, px, T8_dev, A, ts, (float *)workspace_dev, stream))
+        if (int rc = bilin_fwd_tiles(img_dev + (size_t)s0 * H * W, n, H, W, PH, PW, py, px, T8_dev, A, ts, (float *)workspace_dev, stream, fast))
             return rc;
         const RotGeom g{n, H, W, PH, PW, py, px, A};
         return launch_tile_reduce((const float *)workspace_dev, g, ts, T8_dev, sino_dev + (size_t)s0 * A * PW, LogLikEpilogue{}, stream);

@@ -63,7 +63,13 @@ struct BilinRay {
     bool none;            // the ray misses the unit: whatever its lane walks on the interior, its sum is zero
 };
 
-template <int NS, bool TILED, bool PADDED, bool SORTED, bool RS = false>
+// FAST (precision = "fast", opt-in: ctpvae_rotate_fwd_fast_f32 / _tiled_fast_f32): the SAME samples -- coordinates, floors, ownership
+// test, tap addresses, interior ranges and the order of a ray's rows are the exact kernel's, to the bit -- blended as three lerps
+//     t = fma(wx, b - a, a), u = fma(wx, d - c, c), v = fma(wy, u - t, t),   wx = fract(x), wy = fract(y)
+// instead of TensorFlow's ten unfused operations: per slice pair three v_pk_add_f32 and three v_pk_fma_f32, and 1 - wx, 1 - wy are
+// never computed.  The result differs from the exact kernel's by rounding only (~3e-7 of the sinogram's maximum on white noise).
+// The coordinates are NOT fused: an ulp of a coordinate of ~100 px moves a sample by 1e-5 px, which alone costs 1-3e-5 on white noise.
+template <int NS, bool TILED, bool PADDED, bool SORTED, bool RS = false, bool FAST = false>
 __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__restrict__ img, RotGeom gfull, TileSpec ts,
                                                                 const float *__restrict__ T8, int t8_lds_off, float *__restrict__ out)
 {
@@ -240,7 +246,9 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
         return q;
     };
 
-    auto walk = [&](const BilinRay &q, auto mirror_tag) {
+    // (FAST takes the ray BY VALUE: through the reference hipcc kept the four-slice fast kernels' ray in memory -- 32 bytes of scratch per lane,
+    // written and read back once per task; the exact kernels keep the reference and, with it, their instruction streams)
+    auto walk = [&](std::conditional_t<FAST, const BilinRay, const BilinRay &> q, auto mirror_tag) {
         constexpr bool MIRROR = decltype(mirror_tag)::value;
         const f32x2 basex = {q.xj, q.xj}, basey = {q.yj, q.yj}, stepx = {q.t1, q.t1}, stepy = {q.t4, q.t4};
         const f32x2 shiftx = {q.t2, q.t2}, shifty = {q.t5, q.t5};
@@ -251,7 +259,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
         vec_t acc = vec_t(0.0f);
         const int offv = off_v;     // (named here: an outer variable used only inside an asm operand of a nested lambda is not captured)
         struct Pair {               // two consecutive rows of one ray
-            f32x2 wl, wh, wy0, wy1;   // weights of the low / high cell of a pair, of the floor / ceil row
+            f32x2 wl, wh, wy0, wy1;   // weights of the low / high cell of a pair, of the floor / ceil row (FAST: wl = fract(x), wy1 = fract(y) alone)
             vec_t tp[2][4];           // taps: [row][low cell of the floor row, high, low cell of the ceil row, high]
         };
         // One row: floor taps -> ownership test -> byte address of the low cell of the floor row (the all-zero block at LDS
@@ -302,7 +310,15 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
             const f32x2 y = (basey + stepy * fi) + shifty;
             fi += RS ? 4.0f : 2.0f;
             f32x2 wx0, wx1;
-            if constexpr (PADDED) {
+            if constexpr (FAST) {
+                if constexpr (PADDED) {
+                    P.wl = f32x2{__builtin_amdgcn_fractf(x.x), __builtin_amdgcn_fractf(x.y)};
+                    P.wy1 = f32x2{__builtin_amdgcn_fractf(y.x), __builtin_amdgcn_fractf(y.y)};
+                } else {
+                    P.wl = x - f32x2{floorf(x.x), floorf(x.y)};
+                    P.wy1 = y - f32x2{floorf(y.x), floorf(y.y)};
+                }
+            } else if constexpr (PADDED) {
                 wx1 = f32x2{__builtin_amdgcn_fractf(x.x), __builtin_amdgcn_fractf(x.y)};
                 P.wy1 = f32x2{__builtin_amdgcn_fractf(y.x), __builtin_amdgcn_fractf(y.y)};
                 wx0 = 1.0f - wx1;
@@ -313,8 +329,10 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
                 wx0 = xc - x; wx1 = x - xf;
                 P.wy0 = yc - y; P.wy1 = y - yf;
             }
-            P.wl = MIRROR ? wx1 : wx0;
-            P.wh = MIRROR ? wx0 : wx1;
+            if constexpr (!FAST) {
+                P.wl = MIRROR ? wx1 : wx0;
+                P.wh = MIRROR ? wx0 : wx1;
+            }
             row_taps(x.x, y.x, P.tp[0], test_tag);
             row_taps(x.y, y.y, P.tp[1], test_tag);
             __builtin_amdgcn_sched_barrier(0);
@@ -323,11 +341,21 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
             vec_t val[2];
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
+                if constexpr (FAST) {
+                    // lerps from the xf cell towards the xc cell (mirrored angles: the pair arrives as (xc, xf)), then from the floor row
+                    // towards the ceil row; the file is compiled -ffp-contract=off, so these three are the only fused operations
+                    constexpr int F = MIRROR ? 1 : 0, C = MIRROR ? 0 : 1;
+                    const vec_t wx = vec_t(r ? P.wl.y : P.wl.x), wy = vec_t(r ? P.wy1.y : P.wy1.x);
+                    const vec_t v_yf = __builtin_elementwise_fma(wx, P.tp[r][C] - P.tp[r][F], P.tp[r][F]);
+                    const vec_t v_yc = __builtin_elementwise_fma(wx, P.tp[r][2 + C] - P.tp[r][2 + F], P.tp[r][2 + F]);
+                    val[r] = __builtin_elementwise_fma(wy, v_yc - v_yf, v_yf);
+                } else {
                 const float wl = r ? P.wl.y : P.wl.x, wh = r ? P.wh.y : P.wh.x;
                 const float w0 = r ? P.wy0.y : P.wy0.x, w1 = r ? P.wy1.y : P.wy1.x;
                 const vec_t v_yf = wl * P.tp[r][0] + wh * P.tp[r][1];
                 const vec_t v_yc = wl * P.tp[r][2] + wh * P.tp[r][3];
                 val[r] = w0 * v_yf + w1 * v_yc;
+                }
                 if constexpr (!RS) acc += val[r];
             }
             if constexpr (RS) {
@@ -404,10 +432,20 @@ __global__ __launch_bounds__(1024) void rotate_fwd_bilin_kernel(const float *__r
             int ad = __mul24(iyr, pitchB) + off_rows;
             ad = MIRROR ? ad - (ixr << SHIFT) + off_cols : ad + (ixr << SHIFT) + off_cols;
             ad = own ? ad : lds_base;
+            if constexpr (FAST) {
+                const vec_t wx = vec_t(x - xf), wy = vec_t(y - yf);      // (== fract where the sample is live: x, y >= 0 there)
+                const vec_t pa = lds_abs_vec<NS>(MIRROR ? ad + CELL : ad), pb = lds_abs_vec<NS>(MIRROR ? ad : ad + CELL);
+                const vec_t pc = lds_abs_vec<NS>(MIRROR ? ad + pitchB + CELL : ad + pitchB), pd = lds_abs_vec<NS>(MIRROR ? ad + pitchB : ad + pitchB + CELL);
+                const vec_t v_yf = __builtin_elementwise_fma(wx, pb - pa, pa);
+                const vec_t v_yc = __builtin_elementwise_fma(wx, pd - pc, pc);
+                acc += __builtin_elementwise_fma(wy, v_yc - v_yf, v_yf);
+                (void)xc; (void)yc;
+            } else {
             const float wl = MIRROR ? x - xf : xc - x, wh = MIRROR ? xc - x : x - xf;
             const vec_t v_yf = wl * lds_abs_vec<NS>(ad) + wh * lds_abs_vec<NS>(ad + CELL);
             const vec_t v_yc = wl * lds_abs_vec<NS>(ad + pitchB) + wh * lds_abs_vec<NS>(ad + pitchB + CELL);
             acc += (yc - y) * v_yf + (y - yf) * v_yc;
+            }
         }
         if (q.none) acc = vec_t(0.0f);
         if (q.live && (!RS || lane >= 32)) {
@@ -975,7 +1013,7 @@ bool bilin_fwd_whole_ok(int H, int W, int A)
     return bilin_fwd_whole_geometry(H, W) && bilin_img_bytes(H, W, false, 1) + bilin_extra_bytes(A) <= (size_t)kMaxLdsBytes;
 }
 
-template <int NS, bool TILED>
+template <int NS, bool TILED, bool FAST>
 static int launch_bilin_fwd(const float *img_dev, const RotGeom &g, const TileSpec &ts, const float *T8_dev, float *out_dev,
                             ctpvae_stream_t stream)
 {
@@ -1050,10 +1088,20 @@ static int launch_bilin_fwd(const float *img_dev, const RotGeom &g, const TileSp
         CTPVAE_LAUNCH_CHECK("rotate_fwd_bilin_kernel");
         return CTPVAE_OK;
     };
-    if (sorted) return padded ? launch(rotate_fwd_bilin_kernel<NS, TILED, true, true>) : launch(rotate_fwd_bilin_kernel<NS, TILED, false, true>);
+    // (FAST: the same launch shape and task form as the exact kernel's -- every form has its fast twin, none falls back)
+    if (sorted) return padded ? launch(rotate_fwd_bilin_kernel<NS, TILED, true, true, false, FAST>) : launch(rotate_fwd_bilin_kernel<NS, TILED, false, true, false, FAST>);
     if constexpr (!TILED)
-        if (rsplit) return padded ? launch(rotate_fwd_bilin_kernel<NS, false, true, false, true>) : launch(rotate_fwd_bilin_kernel<NS, false, false, false, true>);
-    return padded ? launch(rotate_fwd_bilin_kernel<NS, TILED, true, false>) : launch(rotate_fwd_bilin_kernel<NS, TILED, false, false>);
+        if (rsplit) return padded ? launch(rotate_fwd_bilin_kernel<NS, false, true, false, true, FAST>) : launch(rotate_fwd_bilin_kernel<NS, false, false, false, true, FAST>);
+    return padded ? launch(rotate_fwd_bilin_kernel<NS, TILED, true, false, false, FAST>) : launch(rotate_fwd_bilin_kernel<NS, TILED, false, false, false, FAST>);
+}
+
+template <bool TILED, bool FAST>
+static int launch_bilin_fwd_ns(int ns, const float *img_dev, const RotGeom &g, const TileSpec &ts, const float *T8_dev, float *out_dev,
+                               ctpvae_stream_t stream)
+{
+    if (ns == 4) return launch_bilin_fwd<4, TILED, FAST>(img_dev, g, ts, T8_dev, out_dev, stream);
+    if (ns == 2) return launch_bilin_fwd<2, TILED, FAST>(img_dev, g, ts, T8_dev, out_dev, stream);
+    return launch_bilin_fwd<1, TILED, FAST>(img_dev, g, ts, T8_dev, out_dev, stream);
 }
 
 // slices per LDS cell: as many as fit beside the transform copy (every one shares the sample's index instructions)
@@ -1067,7 +1115,7 @@ static int bilin_fwd_ns(int S, int h, int w, bool tiled, int A)
 
 // whole slices in LDS: [S][H][W] -> [S][A][PW]
 int bilin_fwd_whole(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev, int A,
-                    float *sino_dev, ctpvae_stream_t stream)
+                    float *sino_dev, ctpvae_stream_t stream, bool fast)
 {
     const int ns = bilin_fwd_ns(S, H, W, false, A);
     const TileSpec none{};
@@ -1075,21 +1123,19 @@ int bilin_fwd_whole(const float *img_dev, int S, int H, int W, int PH, int PW, i
         const RotGeom g{n, H, W, PH, PW, py, px, A};
         const float *im = img_dev + (size_t)s0 * H * W;
         float *so = sino_dev + (size_t)s0 * A * PW;
-        if (ns == 4) return launch_bilin_fwd<4, false>(im, g, none, T8_dev, so, stream);
-        if (ns == 2) return launch_bilin_fwd<2, false>(im, g, none, T8_dev, so, stream);
-        return launch_bilin_fwd<1, false>(im, g, none, T8_dev, so, stream);
+        return fast ? launch_bilin_fwd_ns<false, true>(ns, im, g, none, T8_dev, so, stream)
+                    : launch_bilin_fwd_ns<false, false>(ns, im, g, none, T8_dev, so, stream);
     });
 }
 
 // tiles of a slice larger than LDS: partial sums [S / 4][tiles][A][nb][4] into the workspace; the caller runs the reduce pass
 int bilin_fwd_tiles(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev, int A,
-                    const TileSpec &ts, float *workspace_dev, ctpvae_stream_t stream)
+                    const TileSpec &ts, float *workspace_dev, ctpvae_stream_t stream, bool fast)
 {
     const RotGeom g{S, H, W, PH, PW, py, px, A};
     const int ns = bilin_fwd_ns(S, ts.th, ts.tw, true, A);
-    if (ns == 4) return launch_bilin_fwd<4, true>(img_dev, g, ts, T8_dev, workspace_dev, stream);
-    if (ns == 2) return launch_bilin_fwd<2, true>(img_dev, g, ts, T8_dev, workspace_dev, stream);
-    return launch_bilin_fwd<1, true>(img_dev, g, ts, T8_dev, workspace_dev, stream);
+    return fast ? launch_bilin_fwd_ns<true, true>(ns, img_dev, g, ts, T8_dev, workspace_dev, stream)
+                : launch_bilin_fwd_ns<true, false>(ns, img_dev, g, ts, T8_dev, workspace_dev, stream);
 }
 
 // cotangents [S][A][PW] -> gradient images [S][H][W], TensorFlow-compatible, bilinear

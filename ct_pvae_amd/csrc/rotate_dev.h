@@ -145,9 +145,9 @@ bool bilin_fwd_whole_geometry(int H, int W);          // (H, W) is projected who
 bool bilin_fwd_whole_ok(int H, int W, int A);         // ... and this many angles fit beside the image
 bool bilin_fwd_tiles_ok(const TileSpec &ts, int A);   // a tile and this many angles' tables fit LDS
 int bilin_fwd_whole(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev, int A,
-                    float *sino_dev, ctpvae_stream_t stream);
+                    float *sino_dev, ctpvae_stream_t stream, bool fast = false);   // fast: the lerp / FMA blend (precision "fast")
 int bilin_fwd_tiles(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px, const float *T8_dev, int A,
-                    const TileSpec &ts, float *workspace_dev, ctpvae_stream_t stream);
+                    const TileSpec &ts, float *workspace_dev, ctpvae_stream_t stream, bool fast = false);
 // bilinear TensorFlow-compatible backward (rotate_bilin.hip): cotangent segments, slices interleaved per cell
 int bilin_bwd_tfcompat(const float *gsino_dev, int S, int A, int PH, int PW, const float *Tinv8_dev, int H, int W, int py, int px,
                        float *gimg_dev, ctpvae_stream_t stream);

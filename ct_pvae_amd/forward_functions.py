@@ -16,6 +16,12 @@ gets implicitly from TensorFlow:
     backward = "tf_compat" | "exact"    "tf_compat" is what tf.GradientTape computes for the reference
                                         (ctvae/main_ct_vae.py:471-481: the incoming gradient is re-sampled with
                                         the inverted transform); "exact" is the true transpose of the forward.
+    precision = "exact" | "fast"        (bilinear only) "exact", the default, is TensorFlow's unfused blend of a sample's four
+                                        taps, bit for bit the CPU oracle's; "fast" blends them as three fused lerps
+                                        (rotate_fwd_bilin_kernel<..., FAST>): the same samples, results within rounding of the
+                                        exact ones (~3e-7 of the sinogram's maximum; the bar is 1e-5), fewer vector instructions.
+                                        The backward of a fast projection runs the SAME kernels as an exact one's, with the same
+                                        bits: they are the gradient / transpose of the same interpolant.
 """
 import math
 import os
@@ -34,6 +40,14 @@ __all__ = ["pad_phantom", "project_tf_fast", "project_tf_low_mem", "num_proj_pix
 _current_device = getattr(torch._C, "_cuda_getDevice", torch.cuda.current_device)
 _INTERP = {"nearest": _lib.NEAREST, "bilinear": _lib.BILINEAR}
 _BACKWARD = {"tf_compat": _lib.BWD_TF_COMPAT, "exact": _lib.BWD_EXACT}
+_PRECISION = ("exact", "fast")
+
+
+def _check_precision(precision, interp):
+    if precision not in _PRECISION:
+        raise ValueError(f"precision must be one of {list(_PRECISION)} (got {precision!r})")
+    if precision == "fast" and interp != "bilinear":
+        raise ValueError(f"precision='fast' needs interp='bilinear' (got interp={interp!r}): nearest has no weights to blend")
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -176,7 +190,15 @@ def as_angle_index(angles_i, device, keep_host=False):
 class RotatePlan:
     """Geometry and tables of one rotate-and-sum projector: slices [S][H][W] -> sinograms [S][A][PW].
 
-    `forward` / `backward` are the raw operator pair (no autograd bookkeeping); `apply` is differentiable."""
+    `forward` / `backward` are the raw operator pair (no autograd bookkeeping); `apply` is differentiable.
+
+    precision="fast" (interp="bilinear" only; float32 slices only): the forward runs the lerp / FMA instantiation of the bilinear
+    kernel -- every form the dispatcher picks (1 / 2 / 4 slices per cell, plain / row-split / sorted tasks, padded or not, whole
+    slices or halo tiles) has its fast twin, and a launch the bilinear kernel does not take (thousands of angles) raises instead of
+    running an exact kernel.  Under the developer knobs NO_PLAN / FORCE_GENERIC, which select round 1's direct kernels, a fast plan
+    runs the exact direct kernel: those have no fast form.  `backward` (both modes), angle subsets and the float64 gradient kernels
+    are untouched by it: a fast plan's backward is an exact plan's, bit for bit -- the gradient (tf_compat) / transpose (exact) of the
+    same interpolant, from which the fast forward differs by rounding only."""
 
     MAX_SEL = 256   # angles per subset launch of a dense plan (kSelRounds * 64 in rotate_plan.hip)
     # Forward plan format (nearest).  "u16": 2 B per sample (csrc/rotate_plan.hip); "compact": first tap + 2 bits per row,
@@ -199,13 +221,15 @@ class RotatePlan:
     COMPACT_DENSE_WINDOW = (36, 44)
 
     def __init__(self, theta, H, W, pad, device, interp="nearest", backward="tf_compat", use_plan=True, _tables=None,
-                 plan_format="auto"):
+                 plan_format="auto", precision="exact"):
         if plan_format not in ("auto", "compact", "u16"):
             raise ValueError(f"plan_format must be 'auto', 'compact' or 'u16' (got {plan_format!r})")
         if interp not in _INTERP:
             raise ValueError(f"interp must be one of {sorted(_INTERP)} (got {interp!r})")
         if backward not in _BACKWARD:
             raise ValueError(f"backward must be one of {sorted(_BACKWARD)} (got {backward!r})")
+        _check_precision(precision, interp)
+        self.precision, self.fast = precision, precision == "fast"
         self.H, self.W = int(H), int(W)
         if pad:
             P = num_proj_pix(self.H, self.W)
@@ -394,6 +418,8 @@ class RotatePlan:
         return self._fwd_plan, self._compact
 
     def forward_kernel_name(self, S):
+        if self.fast:
+            return "rotate_fwd_bilin_kernel<FAST>"
         if self._fwd_plan is None:
             return "rotate_fwd_fast_kernel"
         return "rotate_fwd_compact_kernel" if self.dense_plan(S)[1] else "rotate_fwd_planned_kernel"
@@ -503,7 +529,8 @@ class RotatePlan:
         idx = as_angle_index(angles_i, self._tdev).long()
         use_plan = False if self._fwd_plan is not None else self._use_tiles
         sub = RotatePlan(None, self.H, self.W, self._pad, self.device, interp=self._interp_name, backward=self._backward_name,
-                         use_plan=use_plan, _tables=(self.T8.index_select(0, idx), self.Tinv8.index_select(0, idx)))
+                         use_plan=use_plan, _tables=(self.T8.index_select(0, idx), self.Tinv8.index_select(0, idx)),
+                         precision=self.precision)
         if key is not None:
             if not use_plan:
                 sub._build_exact_plans()
@@ -544,7 +571,10 @@ class RotatePlan:
     def forward_f64(self, img):
         """float64 slices [S][H][W] -> float64 sinograms [S][A][PW]: fp32 coordinates and weights, float64 taps, products and
         row sum -- TensorFlow's arithmetic for a float64 image (ctvae/tomopy_forward_compare.py:52,56 projects xdesign's float64
-        phantoms).  A correctness-first kernel (ctpvae_rotate_fwd_f64); the float32 paths are untouched."""
+        phantoms).  A correctness-first kernel (ctpvae_rotate_fwd_f64); the float32 paths are untouched.  It has no fast form: a
+        precision="fast" plan refuses float64 slices."""
+        if self.fast:
+            raise ValueError("precision='fast' projects float32 slices only: the float64 path is correctness-first and has no fast form")
         if (img.dim() != 3 or tuple(img.shape[1:]) != (self.H, self.W) or img.dtype is not torch.float64 or not img.is_contiguous()
                 or img.device != self._tdev):
             raise ValueError(f"img must be a contiguous float64 tensor [S][{self.H}][{self.W}] on {self._tdev} "
@@ -704,6 +734,14 @@ class RotatePlan:
                                                                self.px, self.T8.data_ptr(), self.A, self._tplan.data_ptr(),
                                                                ws.data_ptr(), None, None, None, ctypes.c_float(0.0),
                                                                out.data_ptr(), None, None, None, None, _stream_ptr(self._dev_index))
+        elif ws is not None and self.fast:
+            rc = self._lib.ctpvae_rotate_fwd_tiled_fast_f32(img.data_ptr(), S, self.H, self.W, self.PH, self.PW, self.py,
+                                                            self.px, self.T8.data_ptr(), self.A, ws.data_ptr(),
+                                                            out.data_ptr(), _stream_ptr(self._dev_index))
+        elif self.fast:
+            rc = self._lib.ctpvae_rotate_fwd_fast_f32(img.data_ptr(), S, self.H, self.W, self.PH, self.PW, self.py,
+                                                      self.px, self.T8.data_ptr(), self.A, out.data_ptr(),
+                                                      _stream_ptr(self._dev_index))
         elif ws is not None:
             rc = self._lib.ctpvae_rotate_fwd_tiled_interp_f32(img.data_ptr(), S, self.H, self.W, self.PH, self.PW, self.py,
                                                               self.px, self.T8.data_ptr(), self.A, self.interp, ws.data_ptr(),
@@ -1053,7 +1091,7 @@ _DEV_THETA_PLANS = {}   # id(theta tensor) -> (weakref, version, {geometry key: 
 _HOST_THETA_PLANS = {}  # id(theta ndarray) -> (weakref, bytes snapshot, {geometry key: plan})
 
 
-def _cached_plan(theta, H, W, pad, device, interp, backward):
+def _cached_plan(theta, H, W, pad, device, interp, backward, precision="exact"):
     """RotatePlan for this call.  A host-resident angle set (list / numpy / CPU tensor) is keyed by value, so the
     scripts that project with a fixed theta build their tables and gather plans once.  A device-resident theta cannot
     be read without synchronising; it is keyed by the tensor OBJECT (and its in-place version counter), so a caller that
@@ -1061,7 +1099,7 @@ def _cached_plan(theta, H, W, pad, device, interp, backward):
     fresh tensor per call (the reference's per-step tf.gather of theta) rebuilds: pass `angles_i` to
     calculate_log_prob_M_given_R instead, which selects rows of ONE dense plan."""
     if isinstance(theta, torch.Tensor) and theta.device.type == "cuda":
-        geo = (H, W, bool(pad), str(device), interp, backward)
+        geo = (H, W, bool(pad), str(device), interp, backward, precision)
         ent = _DEV_THETA_PLANS.get(id(theta))
         if ent is not None and ent[0]() is theta and ent[1] == theta._version:
             plan = ent[2].get(geo)
@@ -1074,19 +1112,19 @@ def _cached_plan(theta, H, W, pad, device, interp, backward):
                 while len(_DEV_THETA_PLANS) >= _PLAN_CACHE_MAX:
                     _DEV_THETA_PLANS.pop(next(iter(_DEV_THETA_PLANS)))
             ent = _DEV_THETA_PLANS[id(theta)] = (weakref.ref(theta), theta._version, {})
-        plan = ent[2][geo] = RotatePlan(theta, H, W, pad, device, interp=interp, backward=backward)
+        plan = ent[2][geo] = RotatePlan(theta, H, W, pad, device, interp=interp, backward=backward, precision=precision)
         return plan
     if type(theta) is np.ndarray:
         # the same array object as last time (a script's or a trainer's fixed theta): compare its bytes with the snapshot
         # taken when the plan was built (an in-place edit is seen) -- no conversion, no hashing of a new key
         ent = _HOST_THETA_PLANS.get(id(theta))
         if ent is not None and ent[0]() is theta and ent[1] == theta.tobytes():
-            plan = ent[2].get((H, W, pad, device, interp, backward))
+            plan = ent[2].get((H, W, pad, device, interp, backward, precision))
             if plan is not None:
                 return plan
     host = np.ascontiguousarray(np.asarray(theta.detach().cpu() if isinstance(theta, torch.Tensor) else theta,
                                            dtype=np.float32))
-    key = (host.tobytes(), H, W, bool(pad), str(device), interp, backward)
+    key = (host.tobytes(), H, W, bool(pad), str(device), interp, backward, precision)
     plan = _PLAN_CACHE.get(key)
     if type(theta) is np.ndarray and plan is not None:
         ent = _HOST_THETA_PLANS.get(id(theta))
@@ -1095,16 +1133,17 @@ def _cached_plan(theta, H, W, pad, device, interp, backward):
             if len(_HOST_THETA_PLANS) >= 4 * _PLAN_CACHE_MAX:
                 _HOST_THETA_PLANS.clear()
             ent = _HOST_THETA_PLANS[id(theta)] = (weakref.ref(theta), snap, {})
-        ent[2][(H, W, pad, device, interp, backward)] = plan
+        ent[2][(H, W, pad, device, interp, backward, precision)] = plan
     if plan is None:
-        plan = RotatePlan(host, H, W, pad, device, interp=interp, backward=backward)
+        plan = RotatePlan(host, H, W, pad, device, interp=interp, backward=backward, precision=precision)
         if len(_PLAN_CACHE) >= _PLAN_CACHE_MAX:
             _PLAN_CACHE.pop(next(iter(_PLAN_CACHE)))
         _PLAN_CACHE[key] = plan
     return plan
 
 
-def _project(phantom, theta, pad, dim, integrate_vae, interp, backward):
+def _project(phantom, theta, pad, dim, integrate_vae, interp, backward, precision="exact"):
+    _check_precision(precision, interp)
     if not isinstance(phantom, torch.Tensor):
         raise TypeError(f"phantom must be a torch.Tensor on a HIP device (got {type(phantom).__name__})")
     if phantom.device.type != "cuda":
@@ -1127,8 +1166,10 @@ def _project(phantom, theta, pad, dim, integrate_vae, interp, backward):
         layout, H, W = _LAYOUT_DIM2, phantom.shape[0], phantom.shape[1]
     else:
         raise ValueError(f"dim must be 2 or 3 (got {dim})")
+    if precision == "fast" and phantom.dtype is torch.float64:
+        raise ValueError("precision='fast' projects float32 phantoms only: the float64 path is correctness-first and has no fast form")
     dev = phantom.device
-    plan = _cached_plan(theta, H, W, pad, dev, interp, backward)
+    plan = _cached_plan(theta, H, W, pad, dev, interp, backward, precision)
     if dev.index == _current_device():
         if layout == _LAYOUT_VAE and USE_CPP_NODE:
             out = plan.project_vae_cpp(phantom)
@@ -1199,7 +1240,7 @@ def _project_siddon(phantom, theta, pad, dim, integrate_vae):
 
 
 def project_tf_fast(phantom, theta, pad=False, dim=3, integrate_vae=False, *, interp="nearest",
-                    backward="tf_compat", model="rotate"):
+                    backward="tf_compat", model="rotate", precision="exact"):
     """Vectorised Radon forward, ctvae/forward_functions.py:80-123.
 
     phantom: img_size_x x img_size_y x img_size_z (dim=3), img_size_x x img_size_y (dim=2), or
@@ -1213,17 +1254,26 @@ def project_tf_fast(phantom, theta, pad=False, dim=3, integrate_vae=False, *, in
 
     model="siddon" (keyword-only extension): the same layouts through TomoPy's ray-driven projector -- what
     the reference's data were MADE with (scripts/images_to_sinograms.py:62-66) -- differentiable through its exact
-    transpose; `interp` and `backward` do not apply to it."""
+    transpose; `interp`, `backward` and `precision` do not apply to it.
+
+    precision="fast" (keyword-only, with interp="bilinear" and a float32 phantom only; ValueError otherwise): the bilinear forward's
+    lerp / FMA blend, see project_tf_low_mem."""
     if model == "siddon":
         return _project_siddon(phantom, theta, pad, dim, integrate_vae)
     if model != "rotate":
         raise ValueError(f"model must be 'rotate' or 'siddon' (got {model!r})")
-    return _project(phantom, theta, pad, dim, integrate_vae, interp, backward)
+    return _project(phantom, theta, pad, dim, integrate_vae, interp, backward, precision)
 
 
-def project_tf_low_mem(phantom, theta, pad=False, *, interp="bilinear", backward="tf_compat"):
+def project_tf_low_mem(phantom, theta, pad=False, *, interp="bilinear", backward="tf_compat", precision="exact"):
     """Per-angle Radon forward, ctvae/forward_functions.py:49-78: img_size_x x img_size_y x img_size_z ->
     angles x img_size_y x img_size_z, bilinear interpolation.  A float64 phantom is projected and differentiated in float64, as
     in project_tf_fast (fp32 coordinates and weights, double sums; gradient: TensorFlow's for T = double, or the exact
-    transpose)."""
-    return _project(phantom, theta, pad, 3, False, interp, backward)
+    transpose).
+
+    precision="fast" (keyword-only; the default "exact" is TensorFlow's unfused blend, bit for bit the CPU oracle's): the same samples
+    blended as three fused lerps -- within rounding of the exact result (~3e-7 of the sinogram's maximum; the bar is 1e-5), fewer
+    vector instructions in a kernel bound by them.  float32 phantoms and interp="bilinear" only (ValueError otherwise).  The
+    gradient is computed by the SAME backward kernels as for "exact", with the same bits, for both `backward` modes: they are the
+    gradient / transpose of the same interpolant, from which the fast forward differs by rounding only."""
+    return _project(phantom, theta, pad, 3, False, interp, backward, precision)

@@ -154,6 +154,26 @@ int ctpvae_rotate_fwd_tiled_interp_f32(const float *img_dev, int S, int H, int W
                                        const float *T8_dev, int A, int interp, void *workspace_dev, float *sino_dev,
                                        ctpvae_stream_t stream);
 
+/* ---- a5, precision "fast" (round 8, ABI 3400: two added entry points) -- OPT-IN, BILINEAR only ------------------------------------
+ * The bilinear forward above with another blend of the four taps a, b (floor row), c, d (ceil row) of a sample:
+ *     t = fma(wx, b - a, a),  u = fma(wx, d - c, c),  v = fma(wy, u - t, t),   wx = x - floor(x), wy = y - floor(y)
+ * instead of TensorFlow's unfused wy0 (wx0 a + wx1 b) + wy1 (wx0 c + wx1 d): 6 instead of 10 packed operations per slice pair in
+ * a kernel bound by the vector unit's issue rate.  The coordinates x, y, their floors, the taps, the zero fill, the tile a sample
+ * belongs to and the order of every sum are those of ctpvae_rotate_fwd_f32 / ctpvae_rotate_fwd_tiled_interp_f32 with interp =
+ * CTPVAE_BILINEAR, to the bit (the coordinate arithmetic is NOT fused); the result differs from theirs by the rounding of the blend
+ * alone (~3e-7 of the sinogram's maximum on white noise; the bar is 1e-5) and is NOT bit-equal to the oracle.  Deterministic: fixed
+ * bits for fixed arguments.  Arguments as the exact functions' without `interp`; the workspace and tile shape are those of
+ * ctpvae_rotate_fwd_tiled_workspace_bytes / ctpvae_rotate_tile_shape with interp = CTPVAE_BILINEAR; same return codes.
+ * ctpvae_rotate_fwd_fast_f32 takes the calls the bilinear LDS kernel takes (the slice and the tables of A angles fit LDS whole) and
+ * refuses every other with CTPVAE_EINVAL -- it never runs an exact kernel in silence; the one exception are the NO_PLAN /
+ * FORCE_GENERIC knobs of ctpvae_tune_set, which ask for round 1's direct kernels by name: those have no fast form and run as they are.
+ * The backward of a fast forward is ctpvae_rotate_bwd_f32 as before: the gradient / transpose of the same interpolant. */
+int ctpvae_rotate_fwd_fast_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px,
+                               const float *T8_dev, int A, float *sino_dev, ctpvae_stream_t stream);
+int ctpvae_rotate_fwd_tiled_fast_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px,
+                                     const float *T8_dev, int A, void *workspace_dev, float *sino_dev,
+                                     ctpvae_stream_t stream);
+
 /* ... and with the log-likelihood epilogue of ctpvae_rotate_fwd_planned_loglik_f32 (below) in its reduce pass. */
 int ctpvae_rotate_fwd_tiled_loglik_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int py, int px,
                                        const float *T8_dev, int A, void *workspace_dev, const float *mask_dev,
