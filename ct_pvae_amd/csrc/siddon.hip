@@ -17,12 +17,16 @@
 //                                ray-driven accumulation (+ ray table, slow-path flags, the degenerate rays' ray-driven pass);
 //                                optional SIRT store x += A^T upd / sum dist
 //   siddon_rownorm_kernel        sum dist^2 of every ray
+// The training call on this projector (calculate_log_prob_M_given_R(model="siddon"), ctvae/helper_functions.py:336-368): the
+// forward kernels' LIKELIHOOD store (SidLogLik: log-probability and d lp / d ray-sum of every ray-sum, loglik_math.h) and the
+// gather's scaled store, both with the step's angle subset as an index operand into the dense geometry's tables.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 #include "common.h"
 #include "lds_stage.h"
+#include "loglik_math.h"
 
 namespace ctpvae {
 
@@ -185,18 +189,54 @@ __device__ __forceinline__ float siddon_fwd_store(int mode, float sim, const flo
     if (mode == 1) return w != 0.0f ? (meas[o] - sim) / w : 0.0f;
     return (data[o] + w * (sim - meas[o])) / (1.0f + w);
 }
+// The likelihood store of the forward kernels (template flag LL; the stores above are not taken): output row k of every slice is
+// table angle sel[k] (sel == nullptr: k itself) -- g.dt is the number of OUTPUT rows, dt_all the length of the tables -- and the
+// lane that finished a ray evaluates, per slice, LogLikEpilogue's expression on its ray-sum: the functions, in the order, of the
+// planned rotate kernel's epilogue and of loglik_fwd_kernel, so the values are the two-step path's bit for bit.  dense: mask / meas
+// are the [S][dt_all] / [S][dt_all][dx] arrays read at the table angle, else compact like the outputs.  sino / dlp may be null.
+struct SidLogLik {
+    const int *sel;
+    int dt_all;
+    const float *mask, *meas, *pnm;
+    float eps;
+    int dense;
+    float *sino, *lp, *dlp;
+    SidLogLik at_slice(size_t s0, int n_rows, int dx) const
+    {
+        SidLogLik r = *this;
+        const size_t o = s0 * n_rows * dx, sa = s0 * (dense ? dt_all : n_rows);
+        r.mask += sa, r.meas += sa * dx, r.lp += o;
+        if (sino) r.sino += o;
+        if (dlp) r.dlp += o;
+        return r;
+    }
+};
+// an index outside the table cannot leave it (clamped like the planned rotate kernels' sel operand)
+__device__ __forceinline__ int siddon_sel_angle(const int *__restrict__ sel, int k, int dt_all)
+{
+    return sel ? min(max(sel[k], 0), dt_all - 1) : k;
+}
+// Called BEHIND the walk: mask, meas, pnm and its reciprocal are loaded here so that they are not live across it.
+__device__ __forceinline__ void siddon_loglik_store(const SidLogLik &ll, const SidGeom &g, int sl, int k, int pa, int d, float sim)
+{
+    const size_t o = ((size_t)sl * g.dt + k) * g.dx + d;
+    const size_t sa = ll.dense ? (size_t)sl * ll.dt_all + pa : (size_t)sl * g.dt + k;
+    if (ll.sino) ll.sino[o] = sim;
+    LogLikEpilogue ep{ll.mask, ll.meas, ll.pnm, ll.eps, ll.lp, ll.dlp};
+    ep.write(o, sa * g.dx + d, sa, sim);
+}
 typedef float sid_f32x2 __attribute__((ext_vector_type(2)));
 template <int NS> struct SidVec { typedef float type; };
 template <> struct SidVec<2> { typedef sid_f32x2 type; };
 // meas != NULL (SIRT, libtomo sirt.c): instead of the ray-sum `sim` the kernel stores the ray's update factor
 // upd = (meas - sim) / rn2 where rn2 = sum dist^2 != 0, else 0 -- what the back-projector then spreads over the ray.
-template <bool USE_LDS, int NS>
+template <bool USE_LDS, int NS, bool LL>
 __global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restrict__ obj, SidGeom g,
                                                          const float *__restrict__ sin_t,
                                                          const float *__restrict__ cos_t,
                                                          const int *__restrict__ quad_t, int p_per_blk,
                                                          const float *__restrict__ meas, const float *__restrict__ rn2,
-                                                         int mode, float *__restrict__ data)
+                                                         int mode, float *__restrict__ data, SidLogLik ll)
 {
     typedef typename SidVec<NS>::type vec_t;
     static_assert(NS == 1 || USE_LDS, "paired slices live in LDS");
@@ -222,8 +262,9 @@ __global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restric
         const int pl = ray / g.dx;
         const int d = ray - pl * g.dx;
         const int p = p0 + pl;
+        const int pa = LL ? siddon_sel_angle(ll.sel, p, ll.dt_all) : p;     // the table's angle behind output row p
         vec_t acc = 0.0f;
-        siddon_walk_ray(g, sin_t[p], cos_t[p], quad_t[p], d, [&](int ix, int iy, float dist) {
+        siddon_walk_ray(g, sin_t[pa], cos_t[pa], quad_t[pa], d, [&](int ix, int iy, float dist) {
             vec_t m;
             if constexpr (NS == 1)
                 m = USE_LDS ? lds[ix * pitch + iy] : model_g[(size_t)ix * oz + iy];
@@ -232,8 +273,12 @@ __global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restric
             acc += m * dist;
         });
         auto store = [&](int sl, float sim) {
-            const size_t o = ((size_t)sl * g.dt + p) * g.dx + d;
-            data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
+            if constexpr (LL) {
+                siddon_loglik_store(ll, g, sl, p, pa, d, sim);
+            } else {
+                const size_t o = ((size_t)sl * g.dt + p) * g.dx + d;
+                data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
+            }
         };
         if constexpr (NS == 1) {
             store(s, acc);
@@ -262,22 +307,24 @@ __global__ __launch_bounds__(256) void siddon_pack_kernel(const float *__restric
     for (int k = 0; k < NS / 4; ++k) out[k] = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
 }
 
-template <int NS>
+template <int NS, bool LL>
 __global__ __launch_bounds__(256) void siddon_fwd_packed_kernel(const float *__restrict__ packed, SidGeom g,
                                                                const float *__restrict__ sin_t, const float *__restrict__ cos_t,
                                                                const int *__restrict__ quad_t, const float *__restrict__ meas,
-                                                               const float *__restrict__ rn2, int mode, float *__restrict__ data)
+                                                               const float *__restrict__ rn2, int mode, float *__restrict__ data,
+                                                               SidLogLik ll)
 {
     const int grp = blockIdx.y, s0 = grp * NS;
     const int ray = blockIdx.x * blockDim.x + threadIdx.x;
     if (ray >= g.dt * g.dx) return;
     const int p = ray / g.dx, d = ray - p * g.dx;
+    const int pa = LL ? siddon_sel_angle(ll.sel, p, ll.dt_all) : p;
     const int oz = g.oz;
     const float4 *img = reinterpret_cast<const float4 *>(packed + (size_t)grp * g.ox * g.oz * NS);
     float acc[NS], pm[NS], pd = 0.0f;
 #pragma unroll
     for (int k = 0; k < NS; ++k) acc[k] = 0.0f, pm[k] = 0.0f;
-    siddon_walk_ray(g, sin_t[p], cos_t[p], quad_t[p], d, [&](int ix, int iy, float dist) {
+    siddon_walk_ray(g, sin_t[pa], cos_t[pa], quad_t[pa], d, [&](int ix, int iy, float dist) {
 #pragma unroll
         for (int k = 0; k < NS; ++k) acc[k] += pm[k] * pd;       // the previous segment (0 + 0 * 0 the first time)
         const float4 *q = img + (size_t)(ix * oz + iy) * (NS / 4);
@@ -292,8 +339,12 @@ __global__ __launch_bounds__(256) void siddon_fwd_packed_kernel(const float *__r
     for (int k = 0; k < NS; ++k) {
         const float sim = acc[k] + pm[k] * pd;
         if (s0 + k >= g.oy) break;
-        const size_t o = ((size_t)(s0 + k) * g.dt + p) * g.dx + d;
-        data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
+        if constexpr (LL) {
+            siddon_loglik_store(ll, g, s0 + k, p, pa, d, sim);
+        } else {
+            const size_t o = ((size_t)(s0 + k) * g.dt + p) * g.dx + d;
+            data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
+        }
     }
 }
 
@@ -551,23 +602,37 @@ __global__ __launch_bounds__(256) void siddon_gather_flags_kernel(SidGeom g, con
 // The degenerate rays, walked as libtomo walks them, into D[s] (zeroed here; left untouched when the geometry has none):
 // one lane per ray, even rays then odd rays (two rays of one parity are two detector pitches apart and never share a pixel;
 // a degenerate ray's zig-zag stays on its own grid line).
+// The scaled store's angle subset (gather EPI 3, degenerate kernel SEL): row k of `data` (g.dt rows) belongs to angle sel[k] of the
+// DENSE geometry the workspace was prepared for (dt_all angles; sel == nullptr: k itself), and the sums run over k ascending -- the
+// order, and so the bits, of a call on the gathered tables.  scale (or nullptr): slice s is multiplied by scale[s * stride] in
+// the store, once, after its sum.
+struct SidSel {
+    const int *sel;
+    int dt_all;
+    const float *scale;
+    long long scale_stride;
+};
+template <bool SEL>
 __global__ __launch_bounds__(256) void siddon_bwd_degenerate_kernel(const float *__restrict__ data, SidGeom g,
                                                                    const float *__restrict__ sin_t,
                                                                    const float *__restrict__ cos_t,
                                                                    const int *__restrict__ quad_t,
-                                                                   const int *__restrict__ degen_angle, float *__restrict__ D)
+                                                                   const int *__restrict__ degen_angle, float *__restrict__ D,
+                                                                   SidSel ss)
 {
+    auto angle_of = [&](int k) { return SEL ? siddon_sel_angle(ss.sel, k, ss.dt_all) : k; };
     int any = 0;
-    for (int p = threadIdx.x; p < g.dt; p += blockDim.x) any |= degen_angle[p];
+    for (int p = threadIdx.x; p < g.dt; p += blockDim.x) any |= degen_angle[angle_of(p)];
     if (!__syncthreads_or(any)) return;
     const int s = blockIdx.x, npix = g.ox * g.oz;
     float *img = D + (size_t)s * npix;
     for (int t = threadIdx.x; t < npix; t += blockDim.x) img[t] = 0.0f;
     __syncthreads();
     for (int p = 0; p < g.dt; ++p) {
-        if (!degen_angle[p]) continue;
-        const float sin_p = sin_t[p], cos_p = cos_t[p];
-        const int quadrant = quad_t[p];
+        const int pa = angle_of(p);
+        if (!degen_angle[pa]) continue;
+        const float sin_p = sin_t[pa], cos_p = cos_t[pa];
+        const int quadrant = quad_t[pa];
         const float *row = data + ((size_t)s * g.dt + p) * g.dx;
         for (int par = 0; par < 2; ++par) {
             for (int d = 2 * threadIdx.x + par; d < g.dx; d += 2 * blockDim.x) {
@@ -610,13 +675,16 @@ __device__ __forceinline__ void tv_dual_q(const TvPrimal &t, const float *xb, co
 }
 
 // EPI 0: recon = A^T data.   EPI 1 (SIRT): recon += (A^T data) / colsum where colsum != 0 (libtomo sirt.c's last loop).
+// EPI 3 (the training call's backward): recon[s] = scale[s] * (A_sel^T data[s]) over an angle subset of the dense geometry (SidSel).
 template <int NS, int EPI>
 __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     const float *__restrict__ data, SidGeom g, const float *__restrict__ sin_t, const float *__restrict__ cos_t,
     const int *__restrict__ quad_t, const float4 *__restrict__ table, const unsigned *__restrict__ flags,
     const int *__restrict__ degen_angle, const float *__restrict__ D, const float *__restrict__ colsum, int CH, float tau,
-    float *__restrict__ recon, TvPrimal tv)
+    float *__restrict__ recon, TvPrimal tv, SidSel ss)
 {
+    constexpr bool SEL = EPI == 3;
+    auto angle_of = [&](int k) { return SEL ? siddon_sel_angle(ss.sel, k, ss.dt_all) : k; };
     extern __shared__ float lds[];
     // LDS: lines [CH][SEG] float4 | vals [NS][kGatherPlane] | seg_lo [CH] | live [CH] | anyD
     float4 *lines = reinterpret_cast<float4 *>(lds);
@@ -640,7 +708,7 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     __syncthreads();
     {
         int any = 0;
-        for (int p = threadIdx.x; p < g.dt; p += blockDim.x) any |= degen_angle[p];
+        for (int p = threadIdx.x; p < g.dt; p += blockDim.x) any |= degen_angle[angle_of(p)];
         if (any) *any_d = 1;
     }
     __syncthreads();
@@ -652,6 +720,7 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     const float cx_lo = (G.gx0 + (float)ix0) + 0.5f, cx_hi = (G.gx0 + (float)(ix0 + kGatherRows - 1)) + 0.5f;
     const float cy_lo = (G.gy0 + (float)iy0) + 0.5f, cy_hi = (G.gy0 + (float)(iy0 + 63)) + 0.5f;
     unsigned word = 0;
+    [[maybe_unused]] int word_of = -1;        // SEL: which flag word `word` holds (angles arrive in any order)
     for (int p0 = 0; p0 < g.dt; p0 += CH) {
         const int np = min(CH, g.dt - p0);
         __syncthreads();          // the previous chunk has been consumed
@@ -659,8 +728,8 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
         __syncthreads();
         for (int e = threadIdx.x; e < np * kGatherSeg; e += blockDim.x) {
             const int a = e / kGatherSeg, r = e - a * kGatherSeg;
-            const int p = p0 + a;
-            const float sin_p = sin_t[p], cos_p = cos_t[p];
+            const int p = p0 + a, pa = angle_of(p);
+            const float sin_p = sin_t[pa], cos_p = cos_t[pa];
             // every term is monotone in cxp and in cyp: the extremes sit at the corners, with the lanes' own rounding
             const float c00 = cy_lo * cos_p - cx_lo * sin_p, c01 = cy_hi * cos_p - cx_lo * sin_p;
             const float c10 = cy_lo * cos_p - cx_hi * sin_p, c11 = cy_hi * cos_p - cx_hi * sin_p;
@@ -672,7 +741,7 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
 #pragma unroll
             for (int k = 0; k < NS; ++k) v[k] = 0.0f;
             if (d >= 0 && d < g.dx) {
-                line = table[(size_t)p * g.dx + d];
+                line = table[(size_t)pa * g.dx + d];
 #pragma unroll
                 for (int k = 0; k < NS; ++k)
                     if (s0 + k < g.oy) v[k] = data[((size_t)(s0 + k) * g.dt + p) * g.dx + d];
@@ -689,14 +758,21 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
         __syncthreads();
         for (int a = 0; a < np; ++a) {
             const int p = p0 + a;
-            if (a == 0 || (p & 31) == 0) word = mine ? flags[(size_t)(p >> 5) * npix + ix * g.oz + iy] : 0u;
+            if constexpr (!SEL)
+                if (a == 0 || (p & 31) == 0) word = mine ? flags[(size_t)(p >> 5) * npix + ix * g.oz + iy] : 0u;
             if (!live[a]) continue;
-            const float sin_p = sin_t[p], cos_p = cos_t[p];
-            const bool up = quad_t[p] != 0;
+            const int pa = angle_of(p);
+            if constexpr (SEL)
+                if ((pa >> 5) != word_of) {
+                    word_of = pa >> 5;
+                    word = mine ? flags[(size_t)word_of * npix + ix * g.oz + iy] : 0u;
+                }
+            const float sin_p = sin_t[pa], cos_p = cos_t[pa];
+            const bool up = quad_t[pa] != 0;
 #ifdef CTPVAE_TUNE_GATHER_NOSLOW
             const bool slow = false;
 #else
-            const bool slow = (word >> (p & 31)) & 1u;
+            const bool slow = (word >> (pa & 31)) & 1u;
 #endif
             const int r1 = min(max(gather_first_ray(cxp, cyp, sin_p, cos_p, yi0) - seg_lo[a], 0), kGatherSeg - 2);
 #pragma unroll
@@ -728,6 +804,8 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
         } else if constexpr (EPI == 1) {
             const float cs = colsum[ix * g.oz + iy];
             if (cs != 0.0f) *out += acc[k] / cs;
+        } else if constexpr (EPI == 3) {
+            *out = ss.scale ? ss.scale[(size_t)(s0 + k) * ss.scale_stride] * acc[k] : acc[k];
         } else {   // EPI 2: the TV stand-in's primal step (TvPrimal above); `recon` is not written
             const size_t so = (size_t)(s0 + k) * npix, c = (size_t)ix * g.oz + iy;
             const float *xb = tv.xbar_in + so, *qxi = tv.qx_in + so, *qyi = tv.qy_in + so;
@@ -796,21 +874,25 @@ int ctpvae_siddon_tables_f32(const float *theta, int dt, float *sin_out, float *
     return CTPVAE_OK;
 }
 
+// (ll: the likelihood store -- dt is then the number of output rows, the tables have ll->dt_all entries, and meas_dev / rn2_dev /
+// data_dev are not used)
 static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev,
                           const float *cos_dev, const int *quad_dev, int dt, int dx, float center, const float *meas_dev,
-                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream);
+                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr);
 static float siddon_mov(int dx, float center);
 
 static int siddon_fwd_chunks(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                              const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev,
-                             int mode, float *data_dev, ctpvae_stream_t stream)
+                             int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr)
 {
     const int chunk = std::max(2, max_slices_per_launch() / 2 * 2);   // even: whole slice pairs per chunk
     for (int s0 = 0; s0 < oy; s0 += chunk) {
         const int n = std::min(chunk, oy - s0);
+        SidLogLik lls{};
+        if (ll) lls = ll->at_slice((size_t)s0, dt, dx);
         if (int rc = siddon_fwd_one(obj_dev + (size_t)s0 * ox * oz, n, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center,
                                     meas_dev ? meas_dev + (size_t)s0 * dt * dx : nullptr, rn2_dev, mode,
-                                    data_dev + (size_t)s0 * dt * dx, stream))
+                                    data_dev ? data_dev + (size_t)s0 * dt * dx : nullptr, stream, ll ? &lls : nullptr))
             return rc;
     }
     return CTPVAE_OK;
@@ -845,15 +927,19 @@ long long ctpvae_siddon_fwd_workspace_bytes(int oy, int ox, int oz)
 template <int NS>
 static int siddon_fwd_packed(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                              const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev,
-                             int mode, float *packed, float *data_dev, hipStream_t stream)
+                             int mode, float *packed, float *data_dev, hipStream_t stream, const SidLogLik *ll)
 {
     const int npix = ox * oz, groups = ceil_div(oy, NS);
     CTPVAE_REQUIRE(groups <= 65535, "siddon_fwd: at most %d slices per call with a workspace (got %d)", 65535 * NS, oy);
     hipLaunchKernelGGL(siddon_pack_kernel<NS>, dim3(ceil_div(npix, 256), groups), dim3(256), 0, stream, obj_dev, oy, npix, packed);
     CTPVAE_LAUNCH_CHECK("siddon_pack_kernel");
     const SidGeom g{oy, ox, oz, dt, dx, siddon_mov(dx, center)};
-    hipLaunchKernelGGL(siddon_fwd_packed_kernel<NS>, dim3(ceil_div(dt * dx, 256), groups), dim3(256), 0, stream, packed, g, sin_dev,
-                       cos_dev, quad_dev, meas_dev, rn2_dev, mode, data_dev);
+    if (ll)
+        hipLaunchKernelGGL((siddon_fwd_packed_kernel<NS, true>), dim3(ceil_div(dt * dx, 256), groups), dim3(256), 0, stream, packed, g,
+                           sin_dev, cos_dev, quad_dev, meas_dev, rn2_dev, mode, data_dev, *ll);
+    else
+        hipLaunchKernelGGL((siddon_fwd_packed_kernel<NS, false>), dim3(ceil_div(dt * dx, 256), groups), dim3(256), 0, stream, packed, g,
+                           sin_dev, cos_dev, quad_dev, meas_dev, rn2_dev, mode, data_dev, SidLogLik{});
     CTPVAE_LAUNCH_CHECK("siddon_fwd_packed_kernel");
     return CTPVAE_OK;
 }
@@ -862,9 +948,9 @@ extern "C" {
 
 static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                          const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev, int mode,
-                         void *workspace_dev, float *data_dev, ctpvae_stream_t stream)
+                         void *workspace_dev, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr)
 {
-    CTPVAE_REQUIRE(obj_dev && data_dev && sin_dev && cos_dev && quad_dev && oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
+    CTPVAE_REQUIRE(obj_dev && (data_dev || ll) && sin_dev && cos_dev && quad_dev && oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_fwd: null pointer or empty sizes");
     CTPVAE_REQUIRE((meas_dev == nullptr) == (rn2_dev == nullptr), "siddon_fwd: meas and the per-ray weights go together");
     int ns = siddon_packed_ns(oy, ox, oz);
@@ -875,13 +961,13 @@ static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const flo
         (long long)ceil_div(oy, 2) * dt * dx <= 750ll * 64)
         ns = 0;
     if (ns == 0)
-        return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode, data_dev, stream);
+        return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode, data_dev, stream, ll);
     CTPVAE_REQUIRE(workspace_dev, "siddon_fwd: %d slices need the workspace", oy);
     CTPVAE_REQUIRE(((uintptr_t)workspace_dev & 15) == 0, "siddon_fwd: the workspace must be 16-byte aligned");
     return ns == 8 ? siddon_fwd_packed<8>(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode,
-                                          (float *)workspace_dev, data_dev, (hipStream_t)stream)
+                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll)
                    : siddon_fwd_packed<4>(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode,
-                                          (float *)workspace_dev, data_dev, (hipStream_t)stream);
+                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll);
 }
 
 int ctpvae_siddon_fwd_ws_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
@@ -914,9 +1000,9 @@ int ctpvae_siddon_fwd_resid_f32(const float *obj_dev, int oy, int ox, int oz, co
 
 static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev,
                           const float *cos_dev, const int *quad_dev, int dt, int dx, float center, const float *meas_dev,
-                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream)
+                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll)
 {
-    CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && data_dev, "siddon_fwd: null pointer");
+    CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && (data_dev || ll), "siddon_fwd: null pointer");
     CTPVAE_REQUIRE(oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_fwd: sizes must be positive (oy=%d ox=%d oz=%d dt=%d dx=%d)", oy, ox, oz, dt, dx);
     CTPVAE_REQUIRE(oy <= 65535, "siddon_fwd: at most 65535 slices per call (got %d)", oy);
@@ -942,12 +1028,35 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
             CTPVAE_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)shmem));
         hipLaunchKernelGGL(kernel, grid, block, shmem, (hipStream_t)stream, obj_dev, g, sin_dev, cos_dev, quad_dev,
-                           ppb, meas_dev, rn2_dev, mode, data_dev);
+                           ppb, meas_dev, rn2_dev, mode, data_dev, ll ? *ll : SidLogLik{});
         CTPVAE_LAUNCH_CHECK("siddon_fwd_kernel");
         return CTPVAE_OK;
     };
-    if (!use_lds) return launch(siddon_fwd_kernel<false, 1>, 0);
-    return ns == 2 ? launch(siddon_fwd_kernel<true, 2>, lds_bytes) : launch(siddon_fwd_kernel<true, 1>, lds_bytes);
+    if (ll) {
+        if (!use_lds) return launch(siddon_fwd_kernel<false, 1, true>, 0);
+        return ns == 2 ? launch(siddon_fwd_kernel<true, 2, true>, lds_bytes) : launch(siddon_fwd_kernel<true, 1, true>, lds_bytes);
+    }
+    if (!use_lds) return launch(siddon_fwd_kernel<false, 1, false>, 0);
+    return ns == 2 ? launch(siddon_fwd_kernel<true, 2, false>, lds_bytes) : launch(siddon_fwd_kernel<true, 1, false>, lds_bytes);
+}
+
+// The training call's forward (calculate_log_prob_M_given_R(model="siddon")): see the header.
+int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                 const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                 const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
+                                 void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && mask_dev && meas_dev && pnm_dev && lp_dev, "siddon_fwd_loglik: null pointer");
+    CTPVAE_REQUIRE(oy >= 0 && ox > 0 && oz > 0 && dt_all > 0 && dx > 0,
+                   "siddon_fwd_loglik: bad sizes (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox, oz, dt_all, dx);
+    CTPVAE_REQUIRE(sel_dev ? n_sel > 0 : (n_sel == dt_all || n_sel == 0),
+                   "siddon_fwd_loglik: n_sel must be positive with sel_dev, and 0 or dt_all without (got %d, dt_all=%d)", n_sel, dt_all);
+    CTPVAE_REQUIRE(dense == 0 || dense == 1, "siddon_fwd_loglik: dense must be 0 or 1 (got %d)", dense);
+    if (oy == 0) return CTPVAE_OK;
+    const int rows = sel_dev ? n_sel : dt_all;
+    const SidLogLik ll{sel_dev, dt_all, mask_dev, meas_dev, pnm_dev, eps, dense, sino_dev, lp_dev, dlp_dev};
+    return siddon_fwd_ws(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, rows, dx, center, nullptr, nullptr, 0, workspace_dev, nullptr,
+                         stream, &ll);
 }
 
 // ---- back-projector (transpose) and SIRT row weights -----------------------------------------------------------
@@ -1016,7 +1125,8 @@ int ctpvae_siddon_bwd_prepare_f32(int ox, int oz, const float *sin_dev, const fl
 template <int NS>
 static int siddon_gather_launch(const float *data, const SidGeom &g, const float *sin_dev, const float *cos_dev,
                                 const int *quad_dev, const float4 *table, const unsigned *flags, const int *degen,
-                                const float *D, const float *colsum, float *recon, hipStream_t stream, const TvPrimal *tv = nullptr)
+                                const float *D, const float *colsum, float *recon, hipStream_t stream, const TvPrimal *tv = nullptr,
+                                const SidSel *ss = nullptr)
 {
     // angles per LDS chunk: two staging rounds of the 512 threads, ~50 KB with eight slices -> three workgroups per CU
     int CH = std::max(1, std::min(g.dt, kGatherMaxCh));
@@ -1028,10 +1138,11 @@ static int siddon_gather_launch(const float *data, const SidGeom &g, const float
         static std::atomic<unsigned long long> attr_set{0};
         if (shmem > 64 * 1024) CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
         hipLaunchKernelGGL(kernel, grid, block, shmem, stream, data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, D, colsum,
-                           CH, tau, recon, tv ? *tv : TvPrimal{});
+                           CH, tau, recon, tv ? *tv : TvPrimal{}, ss ? *ss : SidSel{});
         CTPVAE_LAUNCH_CHECK("siddon_bwd_gather_kernel");
         return CTPVAE_OK;
     };
+    if (ss) return launch(siddon_bwd_gather_kernel<NS, 3>);
     if (tv) return launch(siddon_bwd_gather_kernel<NS, 2>);
     return colsum ? launch(siddon_bwd_gather_kernel<NS, 1>) : launch(siddon_bwd_gather_kernel<NS, 0>);
 }
@@ -1040,13 +1151,15 @@ extern "C" {
 
 static int siddon_bwd_prepared(const float *data_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                                const int *quad_dev, int dt, int dx, float center, const void *workspace_dev,
-                               const float *colsum_dev, float *recon_dev, ctpvae_stream_t stream, const TvPrimal *tv)
+                               const float *colsum_dev, float *recon_dev, ctpvae_stream_t stream, const TvPrimal *tv,
+                               const SidSel *ss = nullptr)
 {
     CTPVAE_REQUIRE(data_dev && sin_dev && cos_dev && quad_dev && (recon_dev || tv) && workspace_dev, "siddon_bwd: null pointer");
     CTPVAE_REQUIRE(oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_bwd: sizes must be positive (oy=%d ox=%d oz=%d dt=%d dx=%d)", oy, ox, oz, dt, dx);
     CTPVAE_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, "siddon_bwd: the workspace must be 256-byte aligned");
-    const SidWorkspace w = siddon_workspace(oy, ox, oz, dt, dx);
+    // (ss: `dt` rows of data over an angle subset; the workspace is the dense geometry's)
+    const SidWorkspace w = siddon_workspace(oy, ox, oz, ss ? ss->dt_all : dt, dx);
     const float4 *table = (const float4 *)((const char *)workspace_dev + w.off_table);
     const int *degen = (const int *)((const char *)workspace_dev + w.off_degen);
     const unsigned *flags = (const unsigned *)((const char *)workspace_dev + w.off_flags);
@@ -1067,15 +1180,22 @@ static int siddon_bwd_prepared(const float *data_dev, int oy, int ox, int oz, co
                            tv->qx_out + so, tv->qy_out + so};
         }
         const TvPrimal *tvp = tv ? &tvs : nullptr;
-        hipLaunchKernelGGL(siddon_bwd_degenerate_kernel, dim3(g.oy), dim3(256), 0, (hipStream_t)stream, data, g, sin_dev, cos_dev,
-                           quad_dev, degen, Ds);
+        SidSel sss{};
+        if (ss) sss = SidSel{ss->sel, ss->dt_all, ss->scale ? ss->scale + (size_t)s0 * ss->scale_stride : nullptr, ss->scale_stride};
+        const SidSel *ssp = ss ? &sss : nullptr;
+        if (ss)
+            hipLaunchKernelGGL(siddon_bwd_degenerate_kernel<true>, dim3(g.oy), dim3(256), 0, (hipStream_t)stream, data, g, sin_dev, cos_dev,
+                               quad_dev, degen, Ds, sss);
+        else
+            hipLaunchKernelGGL(siddon_bwd_degenerate_kernel<false>, dim3(g.oy), dim3(256), 0, (hipStream_t)stream, data, g, sin_dev, cos_dev,
+                               quad_dev, degen, Ds, SidSel{});
         CTPVAE_LAUNCH_CHECK("siddon_bwd_degenerate_kernel");
         int rc;
         switch (ns) {
-        case 8: rc = siddon_gather_launch<8>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp); break;
-        case 4: rc = siddon_gather_launch<4>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp); break;
-        case 2: rc = siddon_gather_launch<2>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp); break;
-        default: rc = siddon_gather_launch<1>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp); break;
+        case 8: rc = siddon_gather_launch<8>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
+        case 4: rc = siddon_gather_launch<4>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
+        case 2: rc = siddon_gather_launch<2>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
+        default: rc = siddon_gather_launch<1>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
         }
         if (rc) return rc;
     }
@@ -1088,6 +1208,24 @@ int ctpvae_siddon_bwd_prepared_f32(const float *data_dev, int oy, int ox, int oz
 {
     return siddon_bwd_prepared(data_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, workspace_dev, colsum_dev, recon_dev,
                                stream, nullptr);
+}
+
+// The training call's backward (calculate_log_prob_M_given_R(model="siddon")): see the header.
+int ctpvae_siddon_bwd_sel_scaled_f32(const float *data_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                     const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                     const void *workspace_dev, const float *scale_dev, long long scale_stride, float *recon_dev,
+                                     ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(data_dev && sin_dev && cos_dev && quad_dev && workspace_dev && recon_dev, "siddon_bwd_sel_scaled: null pointer");
+    CTPVAE_REQUIRE(oy >= 0 && ox > 0 && oz > 0 && dt_all > 0 && dx > 0,
+                   "siddon_bwd_sel_scaled: bad sizes (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox, oz, dt_all, dx);
+    CTPVAE_REQUIRE(sel_dev ? n_sel > 0 : (n_sel == dt_all || n_sel == 0),
+                   "siddon_bwd_sel_scaled: n_sel must be positive with sel_dev, and 0 or dt_all without (got %d, dt_all=%d)", n_sel, dt_all);
+    CTPVAE_REQUIRE(scale_stride >= 0, "siddon_bwd_sel_scaled: the scale's stride must not be negative");
+    if (oy == 0) return CTPVAE_OK;
+    const SidSel ss{sel_dev, dt_all, scale_dev, scale_stride};
+    return siddon_bwd_prepared(data_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, workspace_dev,
+                               nullptr, recon_dev, stream, nullptr, &ss);
 }
 
 // Round 4: the TV stand-in's primal step as the back-projector's store (TvPrimal above; recon.py _tv).  p_dev [oy][dt][dx] the dual

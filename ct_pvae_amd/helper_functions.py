@@ -3,6 +3,7 @@
     create_sinogram(img, theta, pad=True)                       ctvae/helper_functions.py:33-38
     calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg,
                                  theta=None, angles_i=None, pad=True)   ctvae/helper_functions.py:336-368
+                                 (model="rotate": the reference's rotate-and-sum; model="siddon": TomoPy's ray-driven projector)
 """
 import ctypes
 
@@ -270,8 +271,216 @@ class _ObjectSums(torch.autograd.Function):
         return gout.to(ctx.dtype).view(-1, 1, 1, 1).expand(ctx.shape), None
 
 
+# ---------------------------------------------------------------------------------------------------------
+# a8 on the ray-driven projector: model="siddon"
+# ---------------------------------------------------------------------------------------------------------
+_SIDDON_LOGLIK = {}          # (theta bytes, grid, dx, batch, device) -> _SiddonLogLikState; a few entries
+_SIDDON_LOGLIK_MAX = 4
+
+
+class _SiddonLogLikState:
+    """What the training call on the ray-driven projector keeps per (theta, grid, dx, batch, device): the DENSE angle list's
+    tables, the forward's workspace, the back-projector's workspace prepared once for the dense geometry, and the step's
+    uploaded angle subsets.  Like recon._BP_WORKSPACES: calls that share an entry must be on one stream (the workspaces
+    hold a call's scratch)."""
+    SEL_CACHE_MAX = 8
+
+    def __init__(self, theta_host, B, X, Y, dx, device):
+        self.tables = _siddon_tables(theta_host, device)
+        self.dt, self.B, self.X, self.Y, self.dx, self.device = int(theta_host.size), B, X, Y, dx, device
+        self._fwd_ws = self._bwd_ws = None
+        self._sel = {}
+
+    def fwd_workspace(self):
+        """Device pointer of the forward's workspace (None when the LDS kernels are taken); the size rule follows the
+        library's dispatch, developer knobs included, so it is asked on every call (host arithmetic)."""
+        need = _lib.load().ctpvae_siddon_fwd_workspace_bytes(self.B, self.X, self.Y)
+        _lib.check(need, "siddon_fwd_workspace_bytes")
+        if not need:
+            return None
+        if self._fwd_ws is None or self._fwd_ws.numel() < need:
+            self._fwd_ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+        return self._fwd_ws.data_ptr()
+
+    def bwd_workspace(self):
+        if self._bwd_ws is None:
+            lib = _lib.load()
+            sin_t, cos_t, quad = self.tables
+            need = lib.ctpvae_siddon_bwd_workspace_bytes(self.B, self.X, self.Y, self.dt, self.dx)
+            _lib.check(need, "siddon_bwd_workspace_bytes")
+            ws = torch.empty(int(need), dtype=torch.uint8, device=self.device)
+            _lib.check(lib.ctpvae_siddon_bwd_prepare_f32(self.X, self.Y, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), self.dt,
+                                                         self.dx, ctypes.c_float(self.dx / 2.0), ws.data_ptr(), _stream_ptr()),
+                       "siddon_bwd_prepare")
+            self._bwd_ws = ws
+        return self._bwd_ws.data_ptr()
+
+    def sel(self, angles_i):
+        """The step's subset as an int32 device vector.  Host-resident indices are range-checked as the rotate path checks
+        them (the reference's tf.gather raises on an index outside the list) and uploaded once per value; a device-resident
+        vector cannot be read without a synchronisation and is clamped by the kernels."""
+        t = as_angle_index(angles_i, self.device, keep_host=True)
+        if t.device.type != "cpu":
+            return as_angle_index(t, self.device)
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi >= self.dt:
+            raise ValueError(f"angles_i holds indices outside the {self.dt} angles of theta (min {lo}, max {hi})")
+        key = t.numpy().tobytes()
+        hit = self._sel.get(key)
+        if hit is None:
+            if len(self._sel) >= self.SEL_CACHE_MAX:
+                self._sel.pop(next(iter(self._sel)))
+            hit = self._sel[key] = t.to(self.device)
+        return hit
+
+
+def _siddon_loglik_state(theta, B, X, Y, pad, device):
+    if theta is None:
+        raise ValueError("model='siddon' needs theta")
+    th = np.ascontiguousarray(np.asarray(theta.detach().cpu() if isinstance(theta, torch.Tensor) else theta, dtype=np.float32))
+    if th.ndim != 1 or th.size == 0:
+        raise ValueError(f"theta must be a non-empty 1-D array (got shape {th.shape})")
+    dx = _lib.load().ctpvae_siddon_dx(X, Y, 1 if pad else 0)
+    _lib.check(dx, "siddon_dx")
+    key = (th.tobytes(), X, Y, dx, B, str(device))
+    st = _SIDDON_LOGLIK.get(key)
+    if st is None:
+        if len(_SIDDON_LOGLIK) >= _SIDDON_LOGLIK_MAX:
+            _SIDDON_LOGLIK.pop(next(iter(_SIDDON_LOGLIK)))
+        st = _SIDDON_LOGLIK[key] = _SiddonLogLikState(th, B, X, Y, dx, device)
+    return st
+
+
+def _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel=None, want_sino=False, want_dlp=False):
+    """ONE launch (ctpvae_siddon_fwd_loglik_f32): slices [B][X][Y] -> (ray-sums or None, lp, dlp or None), each [B][rows][dx];
+    sel: int32 device vector of angle numbers into the state's dense tables (mask / meas are then the dense arrays)."""
+    lib = _lib.load()
+    sin_t, cos_t, quad = st.tables
+    B, rows = slices.shape[0], (st.dt if sel is None else sel.numel())
+    shape = (B, rows, st.dx)
+    lp = _fwd._new_output(shape, torch.float32, slices.device)
+    sino = _fwd._new_output(shape, torch.float32, slices.device) if want_sino else None
+    dlp = _fwd._new_output(shape, torch.float32, slices.device) if want_dlp else None
+    _lib.check(lib.ctpvae_siddon_fwd_loglik_f32(
+        slices.data_ptr(), B, st.X, st.Y, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), st.dt, st.dx,
+        ctypes.c_float(st.dx / 2.0), sel.data_ptr() if sel is not None else None, rows, mask.data_ptr(), meas.data_ptr(),
+        1 if sel is not None else 0, pnm.data_ptr(), ctypes.c_float(eps), st.fwd_workspace(),
+        sino.data_ptr() if sino is not None else None, lp.data_ptr(), dlp.data_ptr() if dlp is not None else None, _stream_ptr()),
+        "siddon_fwd_loglik")
+    return sino, lp, dlp
+
+
+def _siddon_backward_scaled(st, data, sel=None, scale=None, scale_stride=0):
+    """ONE launch (ctpvae_siddon_bwd_sel_scaled_f32): data [B][rows][dx] -> scale[b] * (A_sel^T data[b]), [B][X][Y]."""
+    lib = _lib.load()
+    sin_t, cos_t, quad = st.tables
+    B, rows = data.shape[0], data.shape[1]
+    out = _fwd._new_output((B, st.X, st.Y), torch.float32, data.device)
+    _lib.check(lib.ctpvae_siddon_bwd_sel_scaled_f32(
+        data.data_ptr(), B, st.X, st.Y, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), st.dt, st.dx,
+        ctypes.c_float(st.dx / 2.0), sel.data_ptr() if sel is not None else None, rows, st.bwd_workspace(),
+        scale.data_ptr() if scale is not None else None, int(scale_stride), out.data_ptr(), _stream_ptr()), "siddon_bwd_sel_scaled")
+    return out
+
+
+class _SiddonLogLik(torch.autograd.Function):
+    """The training call on the ray-driven projector as ONE node: forward = the projector launch whose store is the
+    log-probability (and d lp / d ray-sum) of every ray-sum, then -- per_object -- the library's same-order reduction of the
+    stored log-probabilities; backward, when only the reconstruction is differentiated, = ONE scaled transpose launch: the
+    upstream gradient of a per-object sum (stride 0 over angles and bins) rides as the per-slice factor, any other upstream
+    multiplies dlp first.  A trainable pnm takes the two-step backward (ctpvae_loglik_bwd_f32, which also reduces d / d pnm)."""
+
+    @staticmethod
+    def forward(ctx, sample, st, mask, meas, pnm, eps, sel, per_object):
+        slices = sample.view(sample.shape[0], sample.shape[1], sample.shape[2])
+        ctx.st, ctx.eps, ctx.sel, ctx.per_object = st, eps, sel, per_object
+        ctx.two_step = ctx.needs_input_grad[4]
+        if ctx.two_step:
+            sino, lp, _ = _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel, want_sino=True)
+            if sel is not None:      # the two-step backward reads compact operands
+                idx = sel.long()
+                mask, meas = mask.index_select(1, idx).contiguous(), meas.index_select(1, idx).contiguous()
+            ctx.save_for_backward(sino, mask, meas, pnm)
+        else:
+            _, lp, dlp = _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel, want_dlp=ctx.needs_input_grad[0])
+            if dlp is not None:
+                ctx.save_for_backward(dlp)
+        if not per_object:
+            return lp.unsqueeze(-1)
+        sums = _fwd._new_output((lp.shape[0],), torch.float32, lp.device)
+        _lib.check(_lib.load().ctpvae_loglik_object_sums_f32(lp.data_ptr(), lp.shape[0], lp.shape[1], lp.shape[2], 0, sums.data_ptr(),
+                                                             _stream_ptr()), "loglik_object_sums")
+        return sums
+
+    @staticmethod
+    def backward(ctx, gout):
+        st, sel = ctx.st, ctx.sel
+        none = (None,) * 7
+        with torch.cuda.device(st.device):
+            if not ctx.two_step:
+                dlp, = ctx.saved_tensors
+                if gout.dtype is not torch.float32:
+                    gout = gout.to(torch.float32)
+                if ctx.per_object:
+                    scale = gout.contiguous()
+                    return (_siddon_backward_scaled(st, dlp, sel, scale, 1).unsqueeze(-1),) + none
+                gout = gout.squeeze(-1)
+                if gout.stride(1) == 0 and gout.stride(2) == 0:
+                    scale = gout[:, 0, 0]
+                    return (_siddon_backward_scaled(st, dlp, sel, scale, scale.stride(0) if scale.shape[0] > 1 else 0).unsqueeze(-1),) + none
+                return (_siddon_backward_scaled(st, gout * dlp, sel).unsqueeze(-1),) + none
+            lib = _lib.load()
+            sino, mask, meas, pnm = ctx.saved_tensors
+            B, A, P = sino.shape
+            g = gout.to(torch.float32)
+            g = (g.view(B, 1, 1).expand(B, A, P) if ctx.per_object else g.squeeze(-1)).contiguous()
+            gproj = _fwd._new_output(sino.shape, sino.dtype, sino.device)
+            gpnm = _fwd._new_output((), torch.float32, sino.device)
+            _lib.check(lib.ctpvae_loglik_bwd_f32(sino.data_ptr(), mask.data_ptr(), meas.data_ptr(), g.data_ptr(), B, A, P, pnm.data_ptr(),
+                                                 ctypes.c_float(ctx.eps), gproj.data_ptr(), gpnm.data_ptr(), _stream_ptr()), "loglik_bwd")
+            gimg = _siddon_backward_scaled(st, gproj, sel).unsqueeze(-1) if ctx.needs_input_grad[0] else None
+        return gimg, None, None, None, gpnm.reshape(pnm.shape), None, None, None
+
+
+def _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce):
+    x = output_sample
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"output_sample must be a torch.Tensor on a HIP device (got {type(x).__name__})")
+    if x.device.type != "cuda":
+        raise _lib.RadonLibraryError(f"output_sample lives on {x.device}: the projector runs on a HIP device only; there is no CPU path")
+    if x.dim() != 4 or x.shape[3] != 1:
+        raise ValueError(f"expected batch_size x img_size_x x img_size_y x 1 (got {tuple(x.shape)})")
+    if not x.dtype.is_floating_point:
+        raise TypeError(f"output_sample must be floating point (got {x.dtype})")
+    in_dtype = x.dtype
+    if x.dtype is not torch.float32 or not x.is_contiguous():
+        x = x.to(torch.float32).contiguous()
+    B, X, Y = x.shape[0], x.shape[1], x.shape[2]
+    st = _siddon_loglik_state(theta, B, X, Y, pad, x.device)
+    sel = st.sel(angles_i) if angles_i is not None else None
+    rows = st.dt if sel is None else sel.numel()
+    pnm = poisson_noise_multiplier
+    if not isinstance(pnm, torch.Tensor):
+        pnm = torch.tensor(float(pnm), dtype=torch.float32, device=x.device)
+    elif pnm.device != x.device or pnm.dtype is not torch.float32:
+        pnm = pnm.to(device=x.device, dtype=torch.float32)
+    if (tuple(mask.shape) != (B, st.dt) or tuple(proj_sample.shape) != (B, st.dt, st.dx) or mask.device != x.device
+            or proj_sample.device != x.device or pnm.numel() != 1):
+        raise ValueError(f"need mask [B][A] and proj_sample [B][A][P] = [{B}][{st.dt}][{st.dx}] on {x.device} "
+                         f"(got {tuple(mask.shape)}, {tuple(proj_sample.shape)})")
+    if B == 0:
+        return x.new_zeros((0,) if reduce == "per_object" else (0, rows, st.dx, 1)).to(in_dtype)
+    if mask.dtype is not torch.float32 or not mask.is_contiguous():
+        mask = mask.to(torch.float32).contiguous()
+    if proj_sample.dtype is not torch.float32 or not proj_sample.is_contiguous():
+        proj_sample = proj_sample.to(torch.float32).contiguous()
+    with torch.cuda.device(x.device):
+        out = _SiddonLogLik.apply(x, st, mask, proj_sample, pnm, float(sqrt_reg), sel, reduce == "per_object")
+    return out if in_dtype is torch.float32 else out.to(in_dtype)
+
+
 def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg,
-                                 theta=None, angles_i=None, pad=True, *, reduce=None):
+                                 theta=None, angles_i=None, pad=True, *, reduce=None, model="rotate"):
     """ctvae/helper_functions.py:336-368.  output_sample [B][X][Y][1], mask [B][angles], proj_sample
     [B][angles][P]; returns the log-probabilities [B][angles_used][P][1].
 
@@ -286,9 +495,23 @@ def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise
     angles_i (the step's random angle subset, :350-357): the plan, the transform tables and the gather plan are built
     ONCE for the whole `theta` (host-resident: on the host, so they are the bits the CPU oracle computes) and the kernels
     take `angles_i` as an index operand -- nothing is gathered or rebuilt per step, and mask / proj_sample are read at
-    the selected angles by the kernel itself."""
+    the selected angles by the kernel itself.
+
+    model="siddon" (keyword-only extension; default "rotate" = every path above): the same call on TomoPy's ray-driven
+    projector, the forward model the reference's data are made with (scripts/images_to_sinograms.py:62-66).  output_sample
+    [B][X][Y][1] is the object stack [oy][ox][oz], the detector has ctpvae_siddon_dx(X, Y, pad) bins (184 at 128 x 128 with
+    pad), center = dx / 2; mask [B][len(theta)], proj_sample [B][len(theta)][dx].  ONE projector launch stores the
+    log-probabilities (the bits of project_tf_fast(model="siddon") followed by gaussian_poisson_log_prob) and d lp / d ray-sum,
+    `angles_i` is an index operand into the dense tables, reduce="per_object" adds the stored values in the library's fixed
+    order, and the backward is ONE scaled transpose launch (deterministic, no atomics).  Tables and workspaces are kept per
+    (theta, grid, batch, device) and used by one stream at a time; after a warm-up call forward + backward allocate nothing
+    but their outputs and can be captured in a HIP graph."""
     if reduce not in (None, "per_object"):
         raise ValueError(f"reduce must be None or 'per_object' (got {reduce!r})")
+    if model != "rotate":
+        if model != "siddon":
+            raise ValueError(f"model must be 'rotate' or 'siddon' (got {model!r})")
+        return _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce)
     x = output_sample
     fast = (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[3] == 1 and x.device.type == "cuda"
             and x.dtype == torch.float32 and x.shape[0] > 0)

@@ -232,7 +232,7 @@ def kl_normal_std(loc, scale):
 # ---------------------------------------------------------------------------------------------------------
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
-                        use_normal=True):
+                        use_normal=True, model="rotate"):
     skips = model_encode(input_encode / 300)
     q = None
     if not deterministic:
@@ -268,7 +268,7 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     # per-object sums of the log-probabilities, reduced inside the projector launch
     lp = calculate_log_prob_M_given_R(output_sample.permute(0, 2, 3, 1), mask.repeat(ns, 1), proj_sample.repeat(ns, 1, 1),
                                       poisson_noise_multiplier, sqrt_reg, theta=theta, angles_i=angles_i, pad=pad,
-                                      reduce="per_object")
+                                      reduce="per_object", model=model)
     # :305-306 reduce_sum(..., axis=[0, 1, 2]) of the squeezed [B][A][P] and [B][X][Y] tensors: the log-likelihood of a
     # sample is ONE number for the whole batch (the batch axis is summed too), the KL below is per object; :329-330 then
     # broadcast-subtract, and train_step takes the mean over the batch -- i.e. mean_b(KL_b) - sum_b(loglik_b).
@@ -413,7 +413,8 @@ class PVAETrainer:
         loss_vec, kl, loglik, _ = find_loss_vae_unsup(proj_sample, mask, input_encode, self.enc, self.dec, pnm_i,
                                                       self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
                                                       theta=self.theta_host, angles_i=angles_i, pad=self.pad,
-                                                      deterministic=a.deterministic, use_normal=a.use_normal)
+                                                      deterministic=a.deterministic, use_normal=a.use_normal,
+                                                      model=getattr(a, "model", "rotate"))
         # ctvae/main_ct_vae.py:478 reduce_mean(loss_M_VAE) / 1e5 = mean_b(KL term) - loglik, where loglik already sums
         # over the batch.  Written so that the ranks' losses ADD UP to the global one (gradients are summed over ranks):
         # each rank contributes its objects' KL / global_B and its own objects' log-likelihood.
@@ -534,7 +535,8 @@ class PVAETrainer:
             loss_vec, _, _, recon = find_loss_vae_unsup(self.proj_samples[sl], self.masks[sl], self.input_encode[sl], self.enc,
                                                         self.dec, self.pnm, self.sqrt_reg, self.kl_anneal, a.klm,
                                                         num_samples=a.ns, theta=self.theta_host, angles_i=None, pad=self.pad,
-                                                        deterministic=a.deterministic, use_normal=a.use_normal)
+                                                        deterministic=a.deterministic, use_normal=a.use_normal,
+                                                        model=getattr(a, "model", "rotate"))
             losses.append(loss_vec.mean() / 1e5)
             recons.append(recon.permute(0, 2, 3, 1))
         loss_final = torch.stack(losses).cpu().numpy()
@@ -572,6 +574,9 @@ def get_args(argv=None):
     p.add_argument("--pnm", type=float, dest="pnm", default=(2 ** 16 - 1) * 0.41)
     p.add_argument("--pnm_start", type=float, dest="pnm_start", default=None)
     p.add_argument("--train_pnm", action="store_true")
+    p.add_argument("--model", choices=["rotate", "siddon"], default="rotate",
+                   help="forward model of the likelihood term: the reference's rotate-and-sum, or the ray-driven projector the "
+                        "datasets are made with (tomopy.project)")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")

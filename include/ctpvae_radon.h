@@ -411,6 +411,31 @@ int ctpvae_siddon_fwd_ws_f32(const float *obj_dev, int oy, int ox, int oz, const
                              void *workspace_dev, float *data_dev, ctpvae_stream_t stream);
 int ctpvae_siddon_rownorm_f32(int ox, int oz, const float *sin_dev, const float *cos_dev, const int *quad_dev, int dt,
                               int dx, float center, float *rn2_dev, ctpvae_stream_t stream);
+/* The likelihood training call on the ray-driven projector (calculate_log_prob_M_given_R(model="siddon"),
+ * ctvae/helper_functions.py:336-368), for the forward model the reference's data were made with.
+ *   _fwd_loglik:  the forward of ctpvae_siddon_fwd_ws_f32 (same dispatch, same workspace rule, same ray-sums) whose store is the
+ *       Gaussian-Poisson log-probability of every ray-sum and, with dlp_dev, d lp / d ray-sum -- the expressions of
+ *       ctpvae_loglik_fwd_f32 in its order: the two-step path's bits.  The tables sin_dev / cos_dev / quad_dev hold dt_all angles;
+ *       sel_dev (int32 [n_sel], device; an index outside the table is clamped into it) picks the step's angles: output row k of
+ *       every slice is table angle sel[k], in any order, repeats allowed; NULL: all dt_all angles (n_sel 0 or dt_all).  With
+ *       rows = n_sel (or dt_all): lp_dev, dlp_dev (or NULL), sino_dev (or NULL: the ray-sums are not stored) [oy][rows][dx];
+ *       dense = 1: mask_dev [oy][dt_all], meas_dev [oy][dt_all][dx] are read at the table angle; dense = 0: [oy][rows],
+ *       [oy][rows][dx].  pnm_dev: one float on the device.  workspace_dev: ctpvae_siddon_fwd_workspace_bytes(oy, ox, oz) bytes
+ *       (NULL when that is 0).
+ *   _bwd_sel_scaled:  recon[s] = scale[s * scale_stride] * (A_sel^T data[s]), data_dev [oy][rows][dx], the transpose of the rows
+ *       above as ctpvae_siddon_bwd_prepared_f32's gather: a pixel's terms arrive in libtomo's order over sel[0 .. n_sel), the
+ *       factor multiplies once, in the store (scale_dev NULL: no factor; stride 0: one factor for the batch).  workspace_dev:
+ *       ctpvae_siddon_bwd_workspace_bytes(>= oy, ox, oz, dt_all, dx) bytes PREPARED for the dense tables (_bwd_prepare, once per
+ *       geometry): a step's subset costs no _prepare.  No atomics: equal bits run to run and to a call on the gathered tables.
+ * oy == 0 returns without a launch; longer batches than a launch takes go in chunks, as in the calls above. */
+int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                 const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                 const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
+                                 void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream);
+int ctpvae_siddon_bwd_sel_scaled_f32(const float *data_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                     const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                     const void *workspace_dev, const float *scale_dev, long long scale_stride, float *recon_dev,
+                                     ctpvae_stream_t stream);
 /* Round 4: an iteration of the TV STAND-IN of tomopy.recon(algorithm='tv') (README.md:221 of the reference asks for 'tv';
  * libtomo's tv.c is NOT restated -- ct_pvae_amd/recon.py says so on every call) as TWO projector launches instead of ~15 torch
  * ops around them: the diagonally preconditioned Chambolle-Pock iteration for min 1/2 |A x - b|^2 + lam TV(x) on K = (A; grad),
