@@ -10,6 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libctpvae_radon.so")
 
 NEAREST, BILINEAR = 0, 1
+NOISE = {"gaussian": 0, "poisson": 1}     # CTPVAE_NOISE_*
 BWD_TF_COMPAT, BWD_EXACT = 0, 1
 EINVAL, EHIP, ENODEV = -1, -2, -3
 ABI_VERSION = 3400   # ctpvae_abi_version() of the library this binding was written for
@@ -38,6 +39,8 @@ SIGNATURES = {
     "ctpvae_rotate_cplan_overflowed": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ctpvae_rotate_fwd_compact_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp,
                                                _vp, _c_int, _vp, _c_float, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_rotate_fwd_compact_noise_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp,
+                                                     _vp, _c_int, _vp, _c_float, _c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_loglik_tasks_per_row": (_c_int, [_c_int, _c_int]),
     "ctpvae_loglik_part_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int]),
     "ctpvae_loglik_object_sums_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
@@ -114,6 +117,8 @@ SIGNATURES = {
                                                  _c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_siddon_fwd_loglik_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _c_int, _vp, _vp,
                                               _c_int, _vp, _c_float, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_siddon_fwd_loglik_noise_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _c_int, _vp,
+                                                    _vp, _c_int, _vp, _c_float, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_siddon_bwd_sel_scaled_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _c_int, _vp,
                                                   _vp, ctypes.c_longlong, _vp, _vp]),
     "ctpvae_siddon_fwd_resid_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp,
@@ -130,6 +135,8 @@ SIGNATURES = {
     "ctpvae_gridrec_tables_host_f32": (_c_int, [_c_int, _c_int, _c_float, _vp, _c_int, _vp, _vp]),
     "ctpvae_gridrec_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "ctpvae_gridrec_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_poisson_loglik_fwd_f32": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_poisson_loglik_bwd_f32": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "ctpvae_loglik_fwd_f32": (_c_int, [_vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_float, _vp, _vp]),
     "ctpvae_poisson_measure_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_ulonglong, _vp, _vp]),
     "ctpvae_philox4x32_10": (_c_int, [_vp, _vp, _vp]),

@@ -44,6 +44,27 @@ __global__ __launch_bounds__(256) void loglik_bwd_kernel(const float *__restrict
     }
 }
 
+// noise = poisson (loglik_math.h): the exact log-probability, elementwise -- the two-step path, and what the fused training calls
+// (rotate_cplan.hip, siddon.hip) are held to bit for bit.  pnm is data: the backward has no d / d pnm.
+__global__ __launch_bounds__(256) void poisson_loglik_fwd_kernel(const float *__restrict__ proj, const float *__restrict__ mask,
+                                                                 const float *__restrict__ x, long long n, int P,
+                                                                 const float *__restrict__ pnm_p, float *__restrict__ out)
+{
+    const float pnm = *pnm_p;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x)
+        out[k] = poisson_logp(proj[k], mask[k / P], x[k], pnm);
+}
+
+__global__ __launch_bounds__(256) void poisson_loglik_bwd_kernel(const float *__restrict__ proj, const float *__restrict__ mask,
+                                                                 const float *__restrict__ x, const float *__restrict__ gout,
+                                                                 long long n, int P, const float *__restrict__ pnm_p,
+                                                                 float *__restrict__ gproj)
+{
+    const float pnm = *pnm_p;
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x)
+        gproj[k] = gout[k] * poisson_dlogp(proj[k], mask[k / P], x[k], pnm);
+}
+
 // Per-object sums of a stored log-probability array in the fixed order of the fused epilogues (LogLikEpilogue::part):
 // a slice's [A][PW] values are cut into 64-lane tasks -- partition 0: the planned kernels' (angle, bin block) tasks, two
 // 32-bin bands mirrored about the detector centre (lane_to_bin); partition 1: the tiled reduce pass's contiguous 64-bin
@@ -104,6 +125,32 @@ int ctpvae_loglik_bwd_f32(const float *proj_dev, const float *mask_dev, const fl
     hipLaunchKernelGGL(loglik_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, proj_dev, mask_dev, x_dev,
                        gout_dev, n, P, pnm_dev, eps, gproj_dev, gpnm_dev);
     CTPVAE_LAUNCH_CHECK("loglik_bwd_kernel");
+    return CTPVAE_OK;
+}
+
+int ctpvae_poisson_loglik_fwd_f32(const float *proj_dev, const float *mask_dev, const float *x_dev, int B, int A, int P,
+                                  const float *pnm_dev, float *out_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(proj_dev && mask_dev && x_dev && pnm_dev && out_dev, "poisson_loglik_fwd: null pointer");
+    CTPVAE_REQUIRE(B > 0 && A > 0 && P > 0, "poisson_loglik_fwd: sizes must be positive (B=%d A=%d P=%d)", B, A, P);
+    const long long n = (long long)B * A * P;
+    const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(poisson_loglik_fwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, proj_dev, mask_dev, x_dev, n, P,
+                       pnm_dev, out_dev);
+    CTPVAE_LAUNCH_CHECK("poisson_loglik_fwd_kernel");
+    return CTPVAE_OK;
+}
+
+int ctpvae_poisson_loglik_bwd_f32(const float *proj_dev, const float *mask_dev, const float *x_dev, const float *gout_dev,
+                                  int B, int A, int P, const float *pnm_dev, float *gproj_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(proj_dev && mask_dev && x_dev && gout_dev && pnm_dev && gproj_dev, "poisson_loglik_bwd: null pointer");
+    CTPVAE_REQUIRE(B > 0 && A > 0 && P > 0, "poisson_loglik_bwd: sizes must be positive (B=%d A=%d P=%d)", B, A, P);
+    const long long n = (long long)B * A * P;
+    const int grid = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(poisson_loglik_bwd_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, proj_dev, mask_dev, x_dev,
+                       gout_dev, n, P, pnm_dev, gproj_dev);
+    CTPVAE_LAUNCH_CHECK("poisson_loglik_bwd_kernel");
     return CTPVAE_OK;
 }
 

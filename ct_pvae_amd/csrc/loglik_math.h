@@ -82,7 +82,54 @@ __device__ __forceinline__ float gaussian_poisson_dlogp(float proj, float m, flo
     return gaussian_poisson_dlogp(gaussian_poisson_terms(proj, m, pnm, eps), m, x, 1.0f / pnm, dpnm);
 }
 
+// ---- noise = poisson: the exact model, tfd.Poisson(rate = proj * mask * pnm).log_prob(x * pnm) (ctvae/toy_mcmc_v2_functions.py:30-64)
+// With k = x * pnm and lam = (proj * mask) * pnm, TFP's expression is  multiply_no_nan(log lam, k) - lgamma(k + 1) - lam.  Its three
+// terms are 1e5 .. 1e7 at the project's pnm and their sum is of order 1 .. 10: in fp32 the textbook form is wrong by 0.1.  Evaluated here
+//   lp = k * (log1p(u) - u) - r(k),   u = (lam - k) / k,   r(k) = lgamma(k + 1) - (k log k - k)      [log1p(u) = log(lam / k)]
+// -- the same value, regrouped so that every term is of the size of the result: k (log1p(u) - u) ~ -(lam - k)^2 / 2k, and r(k), the
+// Stirling remainder, is 0.5 log(2 pi k) + 1 / 12k - 1 / 360k^3 + 1 / 1260k^5 (the next term is 1 / 1680k^7 < 3e-10 from
+// kPoissonStirlingMin on; below it lgammaf and k log k - k are both small and are taken as they stand).  Cases:
+//   k == 0            lp = -lam (lam == 0 included: a masked-out angle scores 0), d lp / d proj = -mask * pnm
+//   lam == 0, k > 0   u = -1, log1p = -inf: lp = -inf
+//   lam < 0           NaN, as TFP (its log rate is NaN); nothing traps
+//   k < 0             -inf (TFP: outside the support), NaN where lam < 0
+// Non-integer k is fine (lgamma, not a factorial).  pnm is data in this model: there is no d / d pnm.  Nothing pins these bits to TFP's.
+constexpr float kPoissonStirlingMin = 8.0f;
+__device__ __forceinline__ float poisson_stirling_remainder(float k)   // r(k), k > 0
+{
+    if (k >= kPoissonStirlingMin) {
+        const float ik = 1.0f / k, ik2 = ik * ik;
+        const float series = ik * (0.083333333333333333f - ik2 * (0.0027777777777777778f - ik2 * 0.00079365079365079365f));
+        return (kHalfLog2Pi + 0.5f * logf(k)) + series;
+    }
+    return lgammaf(k + 1.0f) - (k * logf(k) - k);
+}
+__device__ __forceinline__ float poisson_logp(float proj, float m, float x, float pnm)
+{
+    const float lam = (proj * m) * pnm, k = x * pnm;
+    if (!(k > 0.0f)) {
+        const float ok = k == 0.0f ? -lam : (k < 0.0f ? -__builtin_inff() : k);   // (the last: a NaN k stays NaN)
+        return lam >= 0.0f ? ok : __builtin_nanf("");
+    }
+    const float u = (lam - k) / k;
+    // lam < k / 2: u is near -1 and its own rounding (6e-8 absolute) is a large part of 1 + u = lam / k -- the logarithm is taken
+    // from the quotient there (measured at k = 5.9, lam = 1e-4: 1.5e-2 off through log1p(u), 4e-6 through log(lam / k))
+    const float l1p = u < -0.5f ? logf(lam / k) : log1pf(u);
+    return k * (l1p - u) - poisson_stirling_remainder(k);
+}
+// d lp / d proj (the mask factor included) = mask * pnm * (k - lam) / lam; k == 0: -mask * pnm (multiply_no_nan's gradient: 0 at a
+// masked angle).  Stable as it stands.  It is the formula's derivative, as TFP's autograd gives it, also where lp is not finite:
+// finite at lam < 0 (lp NaN) and at k < 0 (lp -inf), +inf at lam == 0 with k > 0.
+__device__ __forceinline__ float poisson_dlogp(float proj, float m, float x, float pnm)
+{
+    const float mp = m * pnm, lam = (proj * m) * pnm, k = x * pnm;
+    return k == 0.0f ? -mp : mp * ((k - lam) / lam);
+}
+
 // what a projector kernel needs to write log-probabilities next to its ray-sums (lp == nullptr: no epilogue)
+// NOISE (template argument of the evaluating members; 0 = the Gaussian approximation, 1 = poisson): a compile-time selector, so
+// that every Gaussian instantiation keeps the code it had -- only the kernels of the fused training calls (rotate_cplan.hip,
+// siddon.hip) are instantiated a second time.  eps is unused under NOISE = 1.
 struct LogLikEpilogue {
     const float *mask, *meas, *pnm;   // [S][A], [S][A][PW], one value
     float eps;
@@ -112,17 +159,19 @@ struct LogLikEpilogue {
     }
 
     // o: offset of the ray-sum in the outputs; om / sa: offsets of its measured sample and its mask entry
+    template <int NOISE = 0>
     __device__ __forceinline__ void write(size_t o, size_t om, size_t sa, float raysum) const
     {
         const float pnm_v = *pnm;
-        write_loaded(o, mask[sa], meas[om], pnm_v, 1.0f / pnm_v, raysum);
+        write_loaded<NOISE>(o, mask[sa], meas[om], pnm_v, 1.0f / pnm_v, raysum);
     }
     // ... with the operands already in registers (pnm_v = *pnm and its reciprocal, taken once per kernel): a kernel requests them
     // BEFORE its long phase (the walk, the sum over tiles) so that their round trip to memory is not paid after it -- the
     // stores below keep the compiler from moving the loads up by itself (nothing tells it that the buffers are distinct)
+    template <int NOISE = 0>
     __device__ __forceinline__ void write_loaded(size_t o, float m, float x, float pnm_v, float inv_pnm, float raysum) const
     {
-        (void)eval_loaded(o, m, x, pnm_v, inv_pnm, raysum);
+        (void)eval_loaded<NOISE>(o, m, x, pnm_v, inv_pnm, raysum);
     }
     // the same, returning the log-probability; lp (and dlp) are stored only where a buffer was given
     __device__ __forceinline__ float eval(size_t o, size_t om, size_t sa, float raysum) const
@@ -130,8 +179,15 @@ struct LogLikEpilogue {
         const float pnm_v = *pnm;
         return eval_loaded(o, mask[sa], meas[om], pnm_v, 1.0f / pnm_v, raysum);
     }
+    template <int NOISE = 0>
     __device__ __forceinline__ float eval_loaded(size_t o, float m, float x, float pnm_v, float inv_pnm, float raysum) const
     {
+        if constexpr (NOISE == 1) {
+            const float v = poisson_logp(raysum, m, x, pnm_v);
+            if (lp) lp[o] = v;
+            if (dlp) dlp[o] = poisson_dlogp(raysum, m, x, pnm_v);
+            return v;
+        }
         const GaussPoisson t = gaussian_poisson_terms(raysum, m, pnm_v, eps);
         const float v = gaussian_poisson_logp(t, x);
         if (lp) lp[o] = v;

@@ -120,16 +120,18 @@ __global__ __launch_bounds__(64) void rotate_cplan_class_list_kernel(int A, CLay
 // unit with its zero border, builds the step table, then its waves take (angle, bin block) tasks.
 // EPI: 0 = ray-sums only; 1 = + log-probabilities (and d lp / d ray-sum) of the measured samples; 2 = the
 // log-probabilities are REDUCED: one partial sum per task into epi.part (see LogLikEpilogue), d lp / d ray-sum stored for the
-// backward, the ray-sum and log-probability stores only where buffers were given.
+// backward, the ray-sum and log-probability stores only where buffers were given.  3 / 4: 1 / 2 under noise = poisson (the exact
+// log-probability of loglik_math.h in the same stores and sums; the Gaussian instantiations are the code they were).
 // SELM: 0 = all plan angles; 1 = the launch projects a subset of the plan's angles (see rotate_fwd_planned_kernel), read
 // from device memory (sel); 2 = the subset arrived in host memory and travels in the kernel arguments (selh).
-template <int NS, int EPI, int SELM>
+template <int NS, int EPI_ARG, int SELM>
 __global__ __launch_bounds__(1024) void rotate_fwd_compact_kernel(const float *__restrict__ img, PlanGeom g, CLayout L,
                                                                   const char *__restrict__ plan, int wgs_per_slice, int g_S,
                                                                   float *__restrict__ sino, LogLikEpilogue epi,
                                                                   const int *__restrict__ sel, int n_sel, SelHost selh)
 {
     constexpr bool SEL = SELM != 0;
+    constexpr int NOISE = EPI_ARG >= 3 ? 1 : 0, EPI = EPI_ARG >= 3 ? EPI_ARG - 2 : EPI_ARG;
     typedef typename SliceVec<NS>::type vec_t;
     extern __shared__ float lds[];
     float *image = lds + kLutBytes / 4;   // cell c of slice n: image[c * NS + n]
@@ -275,7 +277,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_compact_kernel(const float *_
                 if (live) {
                     const size_t o = ((size_t)sl * A_out + cur.k) * g.PW + cur.j;
                     if (sino) sino[o] = v;
-                    lpv = epi.eval_loaded(o, cur.em[n], cur.ex[n], epnm, einv, v);
+                    lpv = epi.eval_loaded<NOISE>(o, cur.em[n], cur.ex[n], epnm, einv, v);
                 }
                 const float tot = wave_sum(lpv);
                 if (lane == 0) epi.store_part(((size_t)sl * A_out + cur.k) * L.nJB + cur.jb, tot);
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_compact_kernel(const float *_
             auto store = [&](int n, float v) {
                 const size_t o = ((size_t)(s + n) * A_out + cur.k) * g.PW + cur.j;
                 sino[o] = v;
-                if constexpr (EPI == 1) epi.write_loaded(o, cur.em[n], cur.ex[n], epnm, einv, v);
+                if constexpr (EPI == 1) epi.write_loaded<NOISE>(o, cur.em[n], cur.ex[n], epnm, einv, v);
             };
             if constexpr (NS == 1) {
                 store(0, acc);
@@ -359,11 +361,14 @@ int ctpvae_rotate_cplan_overflowed(const void *cplan_dev, int H, int W, int PH, 
     return flag ? 1 : 0;
 }
 
-int ctpvae_rotate_fwd_compact_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *cplan_dev,
-                                  const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
-                                  const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, float *sino_dev,
-                                  float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev, ctpvae_stream_t stream)
+}  // extern "C"
+
+static int rotate_fwd_compact(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *cplan_dev,
+                              const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
+                              const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, int noise, float *sino_dev,
+                              float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev, ctpvae_stream_t stream)
 {
+    CTPVAE_REQUIRE(noise == CTPVAE_NOISE_GAUSSIAN || noise == CTPVAE_NOISE_POISSON, "rotate_fwd_compact: noise must be 0 (gaussian) or 1 (poisson), got %d", noise);
     const int *angle_idx_dev = angle_idx;
     const bool red = lp_sum_dev != nullptr;
     // round 4, built and measured NEGATIVE (tools/time_fold.py, profiles/r04_time_fold.txt): with the knob FOLD_SUMS = 1 the
@@ -461,15 +466,38 @@ int ctpvae_rotate_fwd_compact_f32(const float *img_dev, int S, int H, int W, int
     auto by_ns = [&](auto epi_tag) -> int {
         return ns == 2 ? by_sel(std::integral_constant<int, 2>{}, epi_tag) : by_sel(std::integral_constant<int, 1>{}, epi_tag);
     };
+    const bool pois = noise == CTPVAE_NOISE_POISSON && lik;   // (without an epilogue the model has nothing to select)
     if (red) {
-        if (int rc = by_ns(std::integral_constant<int, 2>{})) return rc;
+        if (int rc = pois ? by_ns(std::integral_constant<int, 4>{}) : by_ns(std::integral_constant<int, 2>{})) return rc;
         if (fold) return CTPVAE_OK;
         hipLaunchKernelGGL(loglik_sum_partials_kernel, dim3(S), dim3(64), 0, (hipStream_t)stream, lp_part_dev, S,
                            A_run, L.nJB, lp_sum_dev);
         CTPVAE_LAUNCH_CHECK("loglik_sum_partials_kernel");
         return CTPVAE_OK;
     }
+    if (pois) return by_ns(std::integral_constant<int, 3>{});
     return lik ? by_ns(std::integral_constant<int, 1>{}) : by_ns(std::integral_constant<int, 0>{});
+}
+
+extern "C" {
+
+int ctpvae_rotate_fwd_compact_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *cplan_dev,
+                                  const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
+                                  const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, float *sino_dev,
+                                  float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev, ctpvae_stream_t stream)
+{
+    return rotate_fwd_compact(img_dev, S, H, W, PH, PW, A, cplan_dev, angle_idx, n_idx, idx_on_host, mask_dev, meas_dev, dense_inputs,
+                              pnm_dev, eps, CTPVAE_NOISE_GAUSSIAN, sino_dev, lp_dev, dlp_dev, lp_part_dev, lp_sum_dev, stream);
+}
+
+int ctpvae_rotate_fwd_compact_noise_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *cplan_dev,
+                                        const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
+                                        const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, int noise,
+                                        float *sino_dev, float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev,
+                                        ctpvae_stream_t stream)
+{
+    return rotate_fwd_compact(img_dev, S, H, W, PH, PW, A, cplan_dev, angle_idx, n_idx, idx_on_host, mask_dev, meas_dev, dense_inputs,
+                              pnm_dev, eps, noise, sino_dev, lp_dev, dlp_dev, lp_part_dev, lp_sum_dev, stream);
 }
 
 }  // extern "C"

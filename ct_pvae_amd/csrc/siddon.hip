@@ -217,26 +217,27 @@ __device__ __forceinline__ int siddon_sel_angle(const int *__restrict__ sel, int
     return sel ? min(max(sel[k], 0), dt_all - 1) : k;
 }
 // Called BEHIND the walk: mask, meas, pnm and its reciprocal are loaded here so that they are not live across it.
+template <int NOISE = 0>
 __device__ __forceinline__ void siddon_loglik_store(const SidLogLik &ll, const SidGeom &g, int sl, int k, int pa, int d, float sim)
 {
     const size_t o = ((size_t)sl * g.dt + k) * g.dx + d;
     const size_t sa = ll.dense ? (size_t)sl * ll.dt_all + pa : (size_t)sl * g.dt + k;
     if (ll.sino) ll.sino[o] = sim;
     LogLikEpilogue ep{ll.mask, ll.meas, ll.pnm, ll.eps, ll.lp, ll.dlp};
-    ep.write(o, sa * g.dx + d, sa, sim);
+    ep.template write<NOISE>(o, sa * g.dx + d, sa, sim);
 }
 typedef float sid_f32x2 __attribute__((ext_vector_type(2)));
 template <int NS> struct SidVec { typedef float type; };
 template <> struct SidVec<2> { typedef sid_f32x2 type; };
 // meas != NULL (SIRT, libtomo sirt.c): instead of the ray-sum `sim` the kernel stores the ray's update factor
 // upd = (meas - sim) / rn2 where rn2 = sum dist^2 != 0, else 0 -- what the back-projector then spreads over the ray.
-template <bool USE_LDS, int NS, bool LL>
-__global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restrict__ obj, SidGeom g,
-                                                         const float *__restrict__ sin_t,
-                                                         const float *__restrict__ cos_t,
-                                                         const int *__restrict__ quad_t, int p_per_blk,
-                                                         const float *__restrict__ meas, const float *__restrict__ rn2,
-                                                         int mode, float *__restrict__ data, SidLogLik ll)
+// (the body of siddon_fwd_kernel / siddon_fwd_poisson_kernel below.  NOISE: the likelihood store's model, loglik_math.h -- the
+// poisson twins are kernels of their own names, so the existing instantiations keep their names and, checked in the disassembly,
+// their code.  The pointers are the kernels' own __restrict__ arguments.)
+template <bool USE_LDS, int NS, bool LL, int NOISE>
+__device__ __forceinline__ void siddon_fwd_body(const float *obj, SidGeom g, const float *sin_t, const float *cos_t, const int *quad_t,
+                                                int p_per_blk, const float *meas, const float *rn2, int mode, float *data,
+                                                const SidLogLik &ll)
 {
     typedef typename SidVec<NS>::type vec_t;
     static_assert(NS == 1 || USE_LDS, "paired slices live in LDS");
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restric
         });
         auto store = [&](int sl, float sim) {
             if constexpr (LL) {
-                siddon_loglik_store(ll, g, sl, p, pa, d, sim);
+                siddon_loglik_store<NOISE>(ll, g, sl, p, pa, d, sim);
             } else {
                 const size_t o = ((size_t)sl * g.dt + p) * g.dx + d;
                 data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
@@ -287,6 +288,27 @@ __global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restric
             if (has2) store(s + 1, acc.y);
         }
     }
+}
+
+template <bool USE_LDS, int NS, bool LL>
+__global__ __launch_bounds__(1024) void siddon_fwd_kernel(const float *__restrict__ obj, SidGeom g,
+                                                         const float *__restrict__ sin_t,
+                                                         const float *__restrict__ cos_t,
+                                                         const int *__restrict__ quad_t, int p_per_blk,
+                                                         const float *__restrict__ meas, const float *__restrict__ rn2,
+                                                         int mode, float *__restrict__ data, SidLogLik ll)
+{
+    siddon_fwd_body<USE_LDS, NS, LL, 0>(obj, g, sin_t, cos_t, quad_t, p_per_blk, meas, rn2, mode, data, ll);
+}
+template <bool USE_LDS, int NS>
+__global__ __launch_bounds__(1024) void siddon_fwd_poisson_kernel(const float *__restrict__ obj, SidGeom g,
+                                                                 const float *__restrict__ sin_t,
+                                                                 const float *__restrict__ cos_t,
+                                                                 const int *__restrict__ quad_t, int p_per_blk,
+                                                                 const float *__restrict__ meas, const float *__restrict__ rn2,
+                                                                 int mode, float *__restrict__ data, SidLogLik ll)
+{
+    siddon_fwd_body<USE_LDS, NS, true, 1>(obj, g, sin_t, cos_t, quad_t, p_per_blk, meas, rn2, mode, data, ll);
 }
 
 // Many slices per walk, from global memory: a grid too large for a PAIR of slices in LDS (184 x 184: the reconstruction grid of
@@ -878,12 +900,13 @@ int ctpvae_siddon_tables_f32(const float *theta, int dt, float *sin_out, float *
 // data_dev are not used)
 static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev,
                           const float *cos_dev, const int *quad_dev, int dt, int dx, float center, const float *meas_dev,
-                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr);
+                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr,
+                          int noise = 0);
 static float siddon_mov(int dx, float center);
 
 static int siddon_fwd_chunks(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                              const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev,
-                             int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr)
+                             int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr, int noise = 0)
 {
     const int chunk = std::max(2, max_slices_per_launch() / 2 * 2);   // even: whole slice pairs per chunk
     for (int s0 = 0; s0 < oy; s0 += chunk) {
@@ -892,7 +915,7 @@ static int siddon_fwd_chunks(const float *obj_dev, int oy, int ox, int oz, const
         if (ll) lls = ll->at_slice((size_t)s0, dt, dx);
         if (int rc = siddon_fwd_one(obj_dev + (size_t)s0 * ox * oz, n, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center,
                                     meas_dev ? meas_dev + (size_t)s0 * dt * dx : nullptr, rn2_dev, mode,
-                                    data_dev ? data_dev + (size_t)s0 * dt * dx : nullptr, stream, ll ? &lls : nullptr))
+                                    data_dev ? data_dev + (size_t)s0 * dt * dx : nullptr, stream, ll ? &lls : nullptr, noise))
             return rc;
     }
     return CTPVAE_OK;
@@ -948,7 +971,7 @@ extern "C" {
 
 static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                          const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev, int mode,
-                         void *workspace_dev, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr)
+                         void *workspace_dev, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr, int noise = 0)
 {
     CTPVAE_REQUIRE(obj_dev && (data_dev || ll) && sin_dev && cos_dev && quad_dev && oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_fwd: null pointer or empty sizes");
@@ -960,8 +983,12 @@ static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const flo
     if (ns != 0 && knob(kKnobSiddonNs) < 0 && 2 * (size_t)ox * (oz + ((1 - (oz & 31)) & 31)) * sizeof(float) <= (size_t)kMaxLdsBytes &&
         (long long)ceil_div(oy, 2) * dt * dx <= 750ll * 64)
         ns = 0;
+    // noise = poisson: the likelihood store has its poisson form in the LDS / global-memory kernels only (the same walk and order
+    // of the sum: the same ray-sums; large batches give up the packed walk, 66-69 against 75.6 us at 32 x 20 in the sweep above;
+    // the Poisson call itself has not been timed)
+    if (ll && noise == CTPVAE_NOISE_POISSON) ns = 0;
     if (ns == 0)
-        return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode, data_dev, stream, ll);
+        return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode, data_dev, stream, ll, noise);
     CTPVAE_REQUIRE(workspace_dev, "siddon_fwd: %d slices need the workspace", oy);
     CTPVAE_REQUIRE(((uintptr_t)workspace_dev & 15) == 0, "siddon_fwd: the workspace must be 16-byte aligned");
     return ns == 8 ? siddon_fwd_packed<8>(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode,
@@ -1000,7 +1027,7 @@ int ctpvae_siddon_fwd_resid_f32(const float *obj_dev, int oy, int ox, int oz, co
 
 static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev,
                           const float *cos_dev, const int *quad_dev, int dt, int dx, float center, const float *meas_dev,
-                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll)
+                          const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll, int noise)
 {
     CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && (data_dev || ll), "siddon_fwd: null pointer");
     CTPVAE_REQUIRE(oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
@@ -1032,6 +1059,10 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
         CTPVAE_LAUNCH_CHECK("siddon_fwd_kernel");
         return CTPVAE_OK;
     };
+    if (ll && noise == CTPVAE_NOISE_POISSON) {
+        if (!use_lds) return launch(siddon_fwd_poisson_kernel<false, 1>, 0);
+        return ns == 2 ? launch(siddon_fwd_poisson_kernel<true, 2>, lds_bytes) : launch(siddon_fwd_poisson_kernel<true, 1>, lds_bytes);
+    }
     if (ll) {
         if (!use_lds) return launch(siddon_fwd_kernel<false, 1, true>, 0);
         return ns == 2 ? launch(siddon_fwd_kernel<true, 2, true>, lds_bytes) : launch(siddon_fwd_kernel<true, 1, true>, lds_bytes);
@@ -1041,11 +1072,12 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
 }
 
 // The training call's forward (calculate_log_prob_M_given_R(model="siddon")): see the header.
-int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
-                                 const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
-                                 const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
-                                 void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream)
+static int siddon_fwd_loglik(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                             const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                             const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps, int noise,
+                             void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream)
 {
+    CTPVAE_REQUIRE(noise == CTPVAE_NOISE_GAUSSIAN || noise == CTPVAE_NOISE_POISSON, "siddon_fwd_loglik: noise must be 0 (gaussian) or 1 (poisson), got %d", noise);
     CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && mask_dev && meas_dev && pnm_dev && lp_dev, "siddon_fwd_loglik: null pointer");
     CTPVAE_REQUIRE(oy >= 0 && ox > 0 && oz > 0 && dt_all > 0 && dx > 0,
                    "siddon_fwd_loglik: bad sizes (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox, oz, dt_all, dx);
@@ -1056,7 +1088,24 @@ int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, c
     const int rows = sel_dev ? n_sel : dt_all;
     const SidLogLik ll{sel_dev, dt_all, mask_dev, meas_dev, pnm_dev, eps, dense, sino_dev, lp_dev, dlp_dev};
     return siddon_fwd_ws(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, rows, dx, center, nullptr, nullptr, 0, workspace_dev, nullptr,
-                         stream, &ll);
+                         stream, &ll, noise);
+}
+int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                 const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                 const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
+                                 void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream)
+{
+    return siddon_fwd_loglik(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt_all, dx, center, sel_dev, n_sel, mask_dev, meas_dev,
+                             dense, pnm_dev, eps, CTPVAE_NOISE_GAUSSIAN, workspace_dev, sino_dev, lp_dev, dlp_dev, stream);
+}
+int ctpvae_siddon_fwd_loglik_noise_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                       const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                       const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
+                                       int noise, void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev,
+                                       ctpvae_stream_t stream)
+{
+    return siddon_fwd_loglik(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt_all, dx, center, sel_dev, n_sel, mask_dev, meas_dev,
+                             dense, pnm_dev, eps, noise, workspace_dev, sino_dev, lp_dev, dlp_dev, stream);
 }
 
 // ---- back-projector (transpose) and SIRT row weights -----------------------------------------------------------

@@ -425,7 +425,14 @@ class RotatePlan:
         return "rotate_fwd_compact_kernel" if self.dense_plan(S)[1] else "rotate_fwd_planned_kernel"
 
     def _run_compact(self, img_ptr, S, out_ptr, angles_i=None, n=0, mask=None, meas=None, dense=0, pnm=None, eps=0.0,
-                     lp_ptr=None, dlp_ptr=None, part_ptr=None, sum_ptr=None):
+                     lp_ptr=None, dlp_ptr=None, part_ptr=None, sum_ptr=None, noise=0):
+        if noise:    # the twin entry point with the noise model as an operand (0 = this one's, so the Gaussian call is unchanged)
+            return self._lib.ctpvae_rotate_fwd_compact_noise_f32(
+                img_ptr, S, self.H, self.W, self.PH, self.PW, self.A, self._fwd_plan.data_ptr(),
+                angles_i.data_ptr() if angles_i is not None else None, n,
+                1 if (angles_i is not None and angles_i.device.type == "cpu") else 0, mask.data_ptr() if mask is not None else None,
+                meas.data_ptr() if meas is not None else None, dense, pnm.data_ptr() if pnm is not None else None,
+                ctypes.c_float(eps), noise, out_ptr, lp_ptr, dlp_ptr, part_ptr, sum_ptr, _stream_ptr(self._dev_index))
         return self._lib.ctpvae_rotate_fwd_compact_f32(
             img_ptr, S, self.H, self.W, self.PH, self.PW, self.A, self._fwd_plan.data_ptr(),
             angles_i.data_ptr() if angles_i is not None else None, n,
@@ -433,16 +440,33 @@ class RotatePlan:
             meas.data_ptr() if meas is not None else None, dense, pnm.data_ptr() if pnm is not None else None,
             ctypes.c_float(eps), out_ptr, lp_ptr, dlp_ptr, part_ptr, sum_ptr, _stream_ptr(self._dev_index))
 
-    def forward_loglik_sums(self, img, mask, meas, pnm, eps, angles_i=None, dense_inputs=False, with_dlp=True):
+    def poisson_fused(self, n_sel=None):
+        """True if noise="poisson" runs inside this plan's projector launch: the step-coded (compact) plan, all its angles or a
+        subset of at most MAX_SEL.  Everything else (u16 plans, tiled slices, longer subsets) has no fused Poisson epilogue."""
+        return self._compact and self.interp == _lib.NEAREST and (n_sel is None or 1 <= n_sel <= self.MAX_SEL)
+
+    def _noise_code(self, noise, angles_i):
+        if noise not in _lib.NOISE:
+            raise ValueError(f"noise must be 'gaussian' or 'poisson' (got {noise!r})")
+        code = _lib.NOISE[noise]
+        if code and not self.poisson_fused(None if angles_i is None else angles_i.numel()):
+            raise ValueError("noise='poisson' is fused into the step-coded (compact) plan's launch only (see poisson_fused): project, "
+                             "then call poisson_log_prob on this geometry")
+        return code
+
+    def forward_loglik_sums(self, img, mask, meas, pnm, eps, angles_i=None, dense_inputs=False, with_dlp=True, noise="gaussian"):
         """Per-object log-likelihood sums (ctvae/helper_functions.py:305-312: reduce_sum of the log-probabilities over
         angles and bins) -> (sums [S], d lp / d ray-sum [S][n][PW] or None), in the library's fixed order
         (ctpvae_loglik_object_sums_f32 / oracle.loglik_object_sums).  On a compact plan the reduction happens INSIDE the
         projector launch: neither the sinogram nor the log-probabilities are written to HBM, only dlp (the
         backward's operand) and one partial per (object, angle, 64-bin task).  Other planned / tiled geometries write the
         log-probabilities and reduce them with the same-order kernel.  Nearest plans only, like forward_loglik: the tiled
-        kernel below has no bilinear form, and its workspace would be the (smaller) bilinear one."""
+        kernel below has no bilinear form, and its workspace would be the (smaller) bilinear one.
+        noise="poisson": the exact Poisson log-probability (poisson_log_prob's bits; eps is ignored) in the same launch, sums and
+        order -- on the compact plan only (`poisson_fused`); other geometries raise."""
         if self.interp != _lib.NEAREST:
             raise ValueError("forward_loglik needs a planned or tiled forward (nearest)")
+        noise = self._noise_code(noise, angles_i)
         if angles_i is not None and not self.sel_supported(angles_i.numel()):
             if dense_inputs:
                 idx = self._sel_dev(angles_i).long()
@@ -488,7 +512,7 @@ class RotatePlan:
             part = self._part_workspace(S, n, 0)
             rc = self._run_compact(img.data_ptr(), S, None, angles_i, n if angles_i is not None else 0, mask, meas,
                                    1 if dense_inputs else 0, pnm, eps, None, dlp.data_ptr() if dlp is not None else None,
-                                   part.data_ptr(), sums.data_ptr())
+                                   part.data_ptr(), sums.data_ptr(), noise=noise)
             if rc:
                 _lib.check(rc, "rotate_fwd_compact")
             return sums, dlp
@@ -617,25 +641,29 @@ class RotatePlan:
         return out
 
     def forward_loglik(self, img, mask, meas, pnm, eps, out=None, out_lp=None, out_dlp=None, with_dlp=False,
-                       angles_i=None, dense_inputs=False):
+                       angles_i=None, dense_inputs=False, noise="gaussian"):
         """Forward with the log-likelihood epilogue (one launch): returns (sino, lp), both [S][A][PW];
         lp = Normal(loc = sino * mask, scale = eps + sqrt(loc / pnm + eps)).log_prob(meas).  Planned and tiled geometries.
         with_dlp: also returns d lp / d sino (third value), which `backward(dlp, scale=...)` turns into the image
         gradient without an elementwise pass.
         angles_i (planned geometries): int32 device vector of plan angles; outputs are [S][len(angles_i)][PW].  With
         dense_inputs, mask [S][A] and meas [S][A][PW] are the DENSE arrays and the kernel reads them at the selected
-        angles (the reference's tf.gather of both, ctvae/helper_functions.py:356-357, costs no launch)."""
+        angles (the reference's tf.gather of both, ctvae/helper_functions.py:356-357, costs no launch).
+        noise="poisson": lp = Poisson(sino * mask * pnm).log_prob(meas * pnm), poisson_log_prob's bits, and its d lp / d sino;
+        eps is ignored.  Fused on the compact plan only (`poisson_fused`, where a dense launch then always takes the compact
+        plan); other geometries raise."""
         if self.interp != _lib.NEAREST:        # before a subset plan is built for nothing
             raise ValueError("forward_loglik needs a planned or tiled forward (nearest)")
+        noise = self._noise_code(noise, angles_i)
         if angles_i is not None and not self.sel_supported(angles_i.numel()):
             if dense_inputs:
                 idx = self._sel_dev(angles_i).long()
                 mask, meas = mask.index_select(1, idx).contiguous(), meas.index_select(1, idx).contiguous()
             return self.subset(angles_i).forward_loglik(img, mask, meas, pnm, eps, out, out_lp, out_dlp, with_dlp)
         if _current_device() == self._dev_index:
-            return self._forward_loglik(img, mask, meas, pnm, eps, out, out_lp, out_dlp, with_dlp, angles_i, dense_inputs)
+            return self._forward_loglik(img, mask, meas, pnm, eps, out, out_lp, out_dlp, with_dlp, angles_i, dense_inputs, noise)
         with torch.cuda.device(self._dev_index):
-            return self._forward_loglik(img, mask, meas, pnm, eps, out, out_lp, out_dlp, with_dlp, angles_i, dense_inputs)
+            return self._forward_loglik(img, mask, meas, pnm, eps, out, out_lp, out_dlp, with_dlp, angles_i, dense_inputs, noise)
 
     def backward(self, gsino, out=None, scale=None, angles_i=None):
         """cotangents [S][A][PW] -> gradient images [S][H][W] (the mode chosen at construction).
@@ -755,7 +783,7 @@ class RotatePlan:
         return out
 
     def _forward_loglik(self, img, mask, meas, pnm, eps, out=None, out_lp=None, out_dlp=None, with_dlp=False,
-                        angles_i=None, dense_inputs=False):
+                        angles_i=None, dense_inputs=False, noise=0):
         self._check(img, (self.H, self.W), "img")
         S = img.shape[0]
         ws = self._tile_workspace(S)
@@ -785,10 +813,10 @@ class RotatePlan:
                 if out_dlp.shape[0] != S:
                     raise ValueError("out_dlp must hold one sinogram per slice")
         dlp_ptr = out_dlp.data_ptr() if out_dlp is not None else None
-        fplan, compact = (self._fwd_plan, self._compact) if (angles_i is not None or self._fwd_plan is None) else self.dense_plan(S)
+        fplan, compact = (self._fwd_plan, self._compact) if (angles_i is not None or self._fwd_plan is None or noise) else self.dense_plan(S)
         if compact:
             rc = self._run_compact(img.data_ptr(), S, out.data_ptr(), angles_i, n if angles_i is not None else 0, mask, meas,
-                                   1 if dense_inputs else 0, pnm, eps, out_lp.data_ptr(), dlp_ptr)
+                                   1 if dense_inputs else 0, pnm, eps, out_lp.data_ptr(), dlp_ptr, noise=noise)
         elif angles_i is not None:
             angles_i = self._sel_dev(angles_i)
             rc = self._lib.ctpvae_rotate_fwd_planned_loglik_sel_f32(

@@ -15,7 +15,7 @@ from . import forward_functions as _fwd  # noqa: E402  (NaN-poisoned outputs in 
 from . import _lib, forward_functions
 from .forward_functions import _cached_plan, _current_device, _stream_ptr, as_angle_index, project_tf_fast
 
-__all__ = ["create_sinogram", "create_sinograms", "calculate_log_prob_M_given_R", "gaussian_poisson_log_prob"]
+__all__ = ["create_sinogram", "create_sinograms", "calculate_log_prob_M_given_R", "gaussian_poisson_log_prob", "poisson_log_prob"]
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -170,6 +170,74 @@ def gaussian_poisson_log_prob(proj, mask, proj_sample, poisson_noise_multiplier,
     return out if proj.dtype == torch.float32 else out.to(proj.dtype)
 
 
+class _PoissonLogProb(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, proj, mask, x, pnm):
+        lib = _lib.load()
+        B, A, P = proj.shape
+        out = _fwd._new_output(proj.shape, proj.dtype, proj.device)
+        with torch.cuda.device(proj.device):
+            _lib.check(lib.ctpvae_poisson_loglik_fwd_f32(proj.data_ptr(), mask.data_ptr(), x.data_ptr(), B, A, P, pnm.data_ptr(),
+                                                         out.data_ptr(), _stream_ptr()), "poisson_loglik_fwd")
+        ctx.save_for_backward(proj, mask, x, pnm)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = _lib.load()
+        proj, mask, x, pnm = ctx.saved_tensors
+        B, A, P = proj.shape
+        gout = gout.contiguous()
+        gproj = _fwd._new_output(proj.shape, proj.dtype, proj.device)
+        with torch.cuda.device(proj.device):
+            _lib.check(lib.ctpvae_poisson_loglik_bwd_f32(proj.data_ptr(), mask.data_ptr(), x.data_ptr(), gout.data_ptr(), B, A, P,
+                                                         pnm.data_ptr(), gproj.data_ptr(), _stream_ptr()), "poisson_loglik_bwd")
+        return gproj, None, None, None
+
+
+def _check_noise(noise, pnm):
+    if noise not in _lib.NOISE:
+        raise ValueError(f"noise must be 'gaussian' or 'poisson' (got {noise!r})")
+    if noise == "poisson" and isinstance(pnm, torch.Tensor) and pnm.requires_grad:
+        raise ValueError("noise='poisson': poisson_noise_multiplier is data in this model (it scales the measured counts): it has no "
+                         "gradient -- pass a number or a tensor that does not require grad")
+    return _lib.NOISE[noise]
+
+
+def poisson_log_prob(proj, mask, proj_sample, poisson_noise_multiplier):
+    """Poisson(rate = proj*mask*pnm).log_prob(proj_sample*pnm), elementwise: the exact model of the measurements
+    (create_all_masks draws Poisson(proj*mask*pnm)/pnm), tfd.Poisson(..., force_probs_to_zero_outside_support=False) of
+    ctvae/toy_mcmc_v2_functions.py:30-64.
+
+    proj, proj_sample [B][A][P]; mask [B][A]; poisson_noise_multiplier a python number or a one-element tensor that does NOT
+    require grad (it is data here: ValueError otherwise).  With k = proj_sample*pnm and lam = proj*mask*pnm:
+    lp = k log lam - lgamma(k + 1) - lam, evaluated in float32 in a form that does not cancel (csrc/loglik_math.h; within ~1e-4
+    of float64 at pnm = 1e4, where the textbook form is wrong by 0.1).  k = 0 gives -lam (0 at a masked angle), lam = 0 with
+    k > 0 gives -inf, lam < 0 NaN; k need not be an integer.  d lp / d proj = mask*pnm*(k - lam)/lam (-mask*pnm at k = 0)."""
+    pnm = poisson_noise_multiplier
+    _check_noise("poisson", pnm)
+    dev = proj.device
+    if dev.type != "cuda":
+        raise _lib.RadonLibraryError(f"proj lives on {dev}: the log-likelihood runs on a HIP device only; there is no CPU path")
+    if proj.dim() != 3 or tuple(proj_sample.shape) != tuple(proj.shape) or tuple(mask.shape) != tuple(proj.shape[:2]):
+        raise ValueError(f"need proj [B][A][P], mask [B][A], proj_sample [B][A][P] (got {tuple(proj.shape)}, "
+                         f"{tuple(mask.shape)}, {tuple(proj_sample.shape)})")
+    if mask.device != dev or proj_sample.device != dev:
+        raise ValueError("proj, mask and proj_sample must live on the same device")
+    if proj.numel() == 0:
+        return proj * 0.0
+    if not isinstance(pnm, torch.Tensor):
+        pnm = torch.tensor(float(pnm), dtype=torch.float32, device=dev)
+    if pnm.numel() != 1:
+        raise ValueError("poisson_noise_multiplier must be a number or a one-element tensor")
+    pnm = pnm.to(device=dev, dtype=torch.float32)
+    if not proj.dtype.is_floating_point:
+        raise TypeError(f"proj must be floating point (got {proj.dtype})")
+    out = _PoissonLogProb.apply(proj.to(torch.float32).contiguous(), mask.to(torch.float32).contiguous(),
+                                proj_sample.to(torch.float32).contiguous(), pnm)
+    return out if proj.dtype == torch.float32 else out.to(proj.dtype)
+
+
 class _ProjectLogLik(torch.autograd.Function):
     """a2 + a8 in one launch: planned / tiled forward with the log-likelihood epilogue.
 
@@ -183,7 +251,7 @@ class _ProjectLogLik(torch.autograd.Function):
     [B][A] / [B][A][P] arrays (dense_inputs) and nothing is gathered, rebuilt or re-planned per step."""
 
     @staticmethod
-    def forward(ctx, sample, plan, mask, x, pnm, eps, angles_i=None):
+    def forward(ctx, sample, plan, mask, x, pnm, eps, angles_i=None, noise="gaussian"):
         # sample: the caller's [B][X][Y][1] tensor (float32, contiguous); re-laid out here, as views, so that the
         # backward pass is this one node (no select_backward: a zero fill and a copy of the whole batch)
         slices = sample.view(sample.shape[0], sample.shape[1], sample.shape[2])
@@ -191,8 +259,13 @@ class _ProjectLogLik(torch.autograd.Function):
         dense = angles_i is not None
         ctx.fused_bwd = ctx.needs_input_grad[0] and not ctx.needs_input_grad[4] and plan.supports_scale
         if ctx.fused_bwd:
-            _, lp, dlp = plan.forward_loglik(slices, mask, x, pnm, eps, with_dlp=True, angles_i=angles_i, dense_inputs=dense)
+            _, lp, dlp = plan.forward_loglik(slices, mask, x, pnm, eps, with_dlp=True, angles_i=angles_i, dense_inputs=dense, noise=noise)
             ctx.save_for_backward(dlp)
+        elif noise != "gaussian":   # reached only when nothing is differentiated: this branch saves nothing for a backward
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[4]:
+                raise ValueError("noise='poisson' has no two-step backward in this node: it needs a plan with the scaled backward "
+                                 "(plan.supports_scale) and a poisson_noise_multiplier that does not require grad")
+            lp =plan.forward_loglik(slices, mask, x, pnm, eps, angles_i=angles_i, dense_inputs=dense, noise=noise)[1]
         else:
             sino, lp = plan.forward_loglik(slices, mask, x, pnm, eps, angles_i=angles_i, dense_inputs=dense)
             if dense:      # the two-step backward reads compact operands
@@ -211,7 +284,7 @@ class _ProjectLogLik(torch.autograd.Function):
                 gimg = ctx.plan.backward(dlp, scale=gout[:, 0, 0], angles_i=ai)
             else:
                 gimg = ctx.plan.backward(gout * dlp, angles_i=ai)
-            return gimg.unsqueeze(-1), None, None, None, None, None, None
+            return gimg.unsqueeze(-1), None, None, None, None, None, None, None
         lib = _lib.load()
         sino, mask, x, pnm = ctx.saved_tensors
         B, A, P = sino.shape
@@ -224,7 +297,7 @@ class _ProjectLogLik(torch.autograd.Function):
                                                  gproj.data_ptr(), gpnm.data_ptr() if gpnm is not None else None,
                                                  _stream_ptr()), "loglik_bwd")
             gimg = ctx.plan.backward(gproj, angles_i=ai).unsqueeze(-1) if ctx.needs_input_grad[0] else None
-        return gimg, None, None, None, (gpnm.reshape(pnm.shape) if gpnm is not None else None), None, None
+        return gimg, None, None, None, (gpnm.reshape(pnm.shape) if gpnm is not None else None), None, None, None
 
 
 class _ProjectLogLikSums(torch.autograd.Function):
@@ -234,10 +307,10 @@ class _ProjectLogLikSums(torch.autograd.Function):
     (a fixed pnm): a trainable pnm takes the two-step path."""
 
     @staticmethod
-    def forward(ctx, sample, plan, mask, x, pnm, eps, angles_i=None):
+    def forward(ctx, sample, plan, mask, x, pnm, eps, angles_i=None, noise="gaussian"):
         slices = sample.view(sample.shape[0], sample.shape[1], sample.shape[2])
         sums, dlp = plan.forward_loglik_sums(slices, mask, x, pnm, eps, angles_i=angles_i, dense_inputs=angles_i is not None,
-                                             with_dlp=ctx.needs_input_grad[0])
+                                             with_dlp=ctx.needs_input_grad[0], noise=noise)
         ctx.plan, ctx.angles_i = plan, angles_i
         if dlp is not None:
             ctx.save_for_backward(dlp)
@@ -248,7 +321,7 @@ class _ProjectLogLikSums(torch.autograd.Function):
         dlp, = ctx.saved_tensors
         scale = gout if gout.dtype is torch.float32 else gout.to(torch.float32)
         gimg = ctx.plan.backward(dlp, scale=scale, angles_i=ctx.angles_i)
-        return gimg.unsqueeze(-1), None, None, None, None, None, None
+        return gimg.unsqueeze(-1), None, None, None, None, None, None, None
 
 
 class _ObjectSums(torch.autograd.Function):
@@ -351,7 +424,7 @@ def _siddon_loglik_state(theta, B, X, Y, pad, device):
     return st
 
 
-def _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel=None, want_sino=False, want_dlp=False):
+def _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel=None, want_sino=False, want_dlp=False, noise=0):
     """ONE launch (ctpvae_siddon_fwd_loglik_f32): slices [B][X][Y] -> (ray-sums or None, lp, dlp or None), each [B][rows][dx];
     sel: int32 device vector of angle numbers into the state's dense tables (mask / meas are then the dense arrays)."""
     lib = _lib.load()
@@ -361,12 +434,15 @@ def _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel=None, want_sino
     lp = _fwd._new_output(shape, torch.float32, slices.device)
     sino = _fwd._new_output(shape, torch.float32, slices.device) if want_sino else None
     dlp = _fwd._new_output(shape, torch.float32, slices.device) if want_dlp else None
-    _lib.check(lib.ctpvae_siddon_fwd_loglik_f32(
-        slices.data_ptr(), B, st.X, st.Y, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), st.dt, st.dx,
-        ctypes.c_float(st.dx / 2.0), sel.data_ptr() if sel is not None else None, rows, mask.data_ptr(), meas.data_ptr(),
-        1 if sel is not None else 0, pnm.data_ptr(), ctypes.c_float(eps), st.fwd_workspace(),
-        sino.data_ptr() if sino is not None else None, lp.data_ptr(), dlp.data_ptr() if dlp is not None else None, _stream_ptr()),
-        "siddon_fwd_loglik")
+    head = (slices.data_ptr(), B, st.X, st.Y, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), st.dt, st.dx,
+            ctypes.c_float(st.dx / 2.0), sel.data_ptr() if sel is not None else None, rows, mask.data_ptr(), meas.data_ptr(),
+            1 if sel is not None else 0, pnm.data_ptr(), ctypes.c_float(eps))
+    tail = (st.fwd_workspace(), sino.data_ptr() if sino is not None else None, lp.data_ptr(),
+            dlp.data_ptr() if dlp is not None else None, _stream_ptr())
+    if noise:    # the twin entry point with the noise model as an operand
+        _lib.check(lib.ctpvae_siddon_fwd_loglik_noise_f32(*head, noise, *tail), "siddon_fwd_loglik_noise")
+    else:
+        _lib.check(lib.ctpvae_siddon_fwd_loglik_f32(*head, *tail), "siddon_fwd_loglik")
     return sino, lp, dlp
 
 
@@ -391,7 +467,7 @@ class _SiddonLogLik(torch.autograd.Function):
     multiplies dlp first.  A trainable pnm takes the two-step backward (ctpvae_loglik_bwd_f32, which also reduces d / d pnm)."""
 
     @staticmethod
-    def forward(ctx, sample, st, mask, meas, pnm, eps, sel, per_object):
+    def forward(ctx, sample, st, mask, meas, pnm, eps, sel, per_object, noise=0):
         slices = sample.view(sample.shape[0], sample.shape[1], sample.shape[2])
         ctx.st, ctx.eps, ctx.sel, ctx.per_object = st, eps, sel, per_object
         ctx.two_step = ctx.needs_input_grad[4]
@@ -402,7 +478,7 @@ class _SiddonLogLik(torch.autograd.Function):
                 mask, meas = mask.index_select(1, idx).contiguous(), meas.index_select(1, idx).contiguous()
             ctx.save_for_backward(sino, mask, meas, pnm)
         else:
-            _, lp, dlp = _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel, want_dlp=ctx.needs_input_grad[0])
+            _, lp, dlp = _siddon_loglik_forward(st, slices, mask, meas, pnm, eps, sel, want_dlp=ctx.needs_input_grad[0], noise=noise)
             if dlp is not None:
                 ctx.save_for_backward(dlp)
         if not per_object:
@@ -415,7 +491,7 @@ class _SiddonLogLik(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         st, sel = ctx.st, ctx.sel
-        none = (None,) * 7
+        none = (None,) * 8
         with torch.cuda.device(st.device):
             if not ctx.two_step:
                 dlp, = ctx.saved_tensors
@@ -439,10 +515,10 @@ class _SiddonLogLik(torch.autograd.Function):
             _lib.check(lib.ctpvae_loglik_bwd_f32(sino.data_ptr(), mask.data_ptr(), meas.data_ptr(), g.data_ptr(), B, A, P, pnm.data_ptr(),
                                                  ctypes.c_float(ctx.eps), gproj.data_ptr(), gpnm.data_ptr(), _stream_ptr()), "loglik_bwd")
             gimg = _siddon_backward_scaled(st, gproj, sel).unsqueeze(-1) if ctx.needs_input_grad[0] else None
-        return gimg, None, None, None, gpnm.reshape(pnm.shape), None, None, None
+        return gimg, None, None, None, gpnm.reshape(pnm.shape), None, None, None, None
 
 
-def _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce):
+def _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce, noise=0):
     x = output_sample
     if not isinstance(x, torch.Tensor):
         raise TypeError(f"output_sample must be a torch.Tensor on a HIP device (got {type(x).__name__})")
@@ -475,12 +551,12 @@ def _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier,
     if proj_sample.dtype is not torch.float32 or not proj_sample.is_contiguous():
         proj_sample = proj_sample.to(torch.float32).contiguous()
     with torch.cuda.device(x.device):
-        out = _SiddonLogLik.apply(x, st, mask, proj_sample, pnm, float(sqrt_reg), sel, reduce == "per_object")
+        out = _SiddonLogLik.apply(x, st, mask, proj_sample, pnm, float(sqrt_reg), sel, reduce == "per_object", noise)
     return out if in_dtype is torch.float32 else out.to(in_dtype)
 
 
 def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg,
-                                 theta=None, angles_i=None, pad=True, *, reduce=None, model="rotate"):
+                                 theta=None, angles_i=None, pad=True, *, reduce=None, model="rotate", noise="gaussian"):
     """ctvae/helper_functions.py:336-368.  output_sample [B][X][Y][1], mask [B][angles], proj_sample
     [B][angles][P]; returns the log-probabilities [B][angles_used][P][1].
 
@@ -505,13 +581,26 @@ def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise
     `angles_i` is an index operand into the dense tables, reduce="per_object" adds the stored values in the library's fixed
     order, and the backward is ONE scaled transpose launch (deterministic, no atomics).  Tables and workspaces are kept per
     (theta, grid, batch, device) and used by one stream at a time; after a warm-up call forward + backward allocate nothing
-    but their outputs and can be captured in a HIP graph."""
+    but their outputs and can be captured in a HIP graph.
+
+    noise="poisson" (keyword-only extension; default "gaussian" = everything above, bit for bit): the EXACT model of the
+    measurements instead of its Gaussian approximation -- Poisson(proj*mask*pnm).log_prob(proj_sample*pnm), the term the
+    reference differentiates for HMC (ctvae/toy_mcmc_v2_functions.py:30-64); see poisson_log_prob for the definition and its edge
+    cases.  sqrt_reg is accepted and IGNORED (the model has no regulariser), and poisson_noise_multiplier is data: one that
+    requires grad raises ValueError before any launch.  FUSED into the projector launch (values and reconstruction gradients
+    equal project_tf_fast followed by poisson_log_prob bit for bit; the backward is the same single scaled launch): model="siddon"
+    always; model="rotate" on the step-coded (compact) plan -- float32 slices that fit LDS, padded, 64 angles or more in `theta`,
+    all of them or a subset of at most 256.  NOT fused -- project_tf_fast, then poisson_log_prob, then the library's fixed-order
+    per-object sums, three launches and autograd's two-step backward: tiled slices (512 x 512), few-angle (u16) plans, subsets of
+    more than 256 angles, and tensors the fast path refuses (other dtypes, non-CUDA).  The C++ autograd node is Gaussian-only."""
     if reduce not in (None, "per_object"):
         raise ValueError(f"reduce must be None or 'per_object' (got {reduce!r})")
+    noise_code = _check_noise(noise, poisson_noise_multiplier)
     if model != "rotate":
         if model != "siddon":
             raise ValueError(f"model must be 'rotate' or 'siddon' (got {model!r})")
-        return _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce)
+        return _siddon_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce,
+                                noise_code)
     x = output_sample
     fast = (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[3] == 1 and x.device.type == "cuda"
             and x.dtype == torch.float32 and x.shape[0] > 0)
@@ -520,6 +609,12 @@ def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise
             x = x.contiguous()
         slices = x       # (shapes below: [B][X][Y][1])
         plan = _cached_plan(theta, x.shape[1], x.shape[2], pad, x.device, "nearest", "tf_compat")
+        if noise_code and not (plan.supports_scale and plan.poisson_fused(
+                None if angles_i is None else as_angle_index(angles_i, x.device, keep_host=True).numel())):
+            # no fused Poisson epilogue on this geometry.  The sums take the partition of the slice size (tiled or not), which the
+            # gathered theta's plan shares with this one; the sum is the same ordered sum under either.
+            return _two_step_log_prob(x, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce,
+                                      noise_code, 0 if plan.planned[0] else 1)
         if plan.planned[0] or plan.tiled:
             sel = None
             if angles_i is not None:
@@ -545,9 +640,12 @@ def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise
             if reduce == "per_object":
                 with torch.cuda.device(x.device):
                     if not pnm.requires_grad and plan.supports_scale:
-                        return _ProjectLogLikSums.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel)
+                        return _ProjectLogLikSums.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel, noise)
                     lp4 = _ProjectLogLik.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel)
                     return _ObjectSums.apply(lp4, 0 if plan.planned[0] else 1)
+            if noise_code:       # (never the C++ node: it is Gaussian-only)
+                with torch.cuda.device(x.device):
+                    return _ProjectLogLik.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel, noise)
             if x.device.index == _current_device():
                 if (forward_functions.USE_CPP_NODE and plan.planned[0] and x.requires_grad and not pnm.requires_grad
                         and torch.is_grad_enabled()):
@@ -557,13 +655,24 @@ def calculate_log_prob_M_given_R(output_sample, mask, proj_sample, poisson_noise
                 return _ProjectLogLik.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel)
             with torch.cuda.device(x.device):
                 return _ProjectLogLik.apply(x, plan, mask, proj_sample, pnm, float(sqrt_reg), sel)
+    return _two_step_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce,
+                              noise_code, 0)
+
+
+def _two_step_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplier, sqrt_reg, theta, angles_i, pad, reduce, noise_code,
+                       partition):
+    """calculate_log_prob_M_given_R without a fused launch: project_tf_fast on the gathered theta, the elementwise log-probability
+    of the noise model, and for reduce="per_object" the library's fixed-order sums over the task partition `partition`."""
     if angles_i is not None:
         angles_i = torch.as_tensor(angles_i, device=output_sample.device).long()
         theta = torch.as_tensor(theta, device=output_sample.device)[angles_i].to(torch.float32)
         mask = mask[:, angles_i]
         proj_sample = proj_sample[:, angles_i]
     proj = project_tf_fast(output_sample, theta, pad=pad, dim=2, integrate_vae=True)
-    logp = gaussian_poisson_log_prob(proj[..., 0], mask, proj_sample, poisson_noise_multiplier, sqrt_reg)
+    if noise_code:
+        logp = poisson_log_prob(proj[..., 0], mask, proj_sample, poisson_noise_multiplier)
+    else:
+        logp = gaussian_poisson_log_prob(proj[..., 0], mask, proj_sample, poisson_noise_multiplier, sqrt_reg)
     if reduce == "per_object":
-        return _ObjectSums.apply(logp.unsqueeze(-1), 0)
+        return _ObjectSums.apply(logp.unsqueeze(-1), partition)
     return logp.unsqueeze(-1)

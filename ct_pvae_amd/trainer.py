@@ -232,7 +232,7 @@ def kl_normal_std(loc, scale):
 # ---------------------------------------------------------------------------------------------------------
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
-                        use_normal=True, model="rotate"):
+                        use_normal=True, model="rotate", noise="gaussian"):
     skips = model_encode(input_encode / 300)
     q = None
     if not deterministic:
@@ -268,7 +268,7 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     # per-object sums of the log-probabilities, reduced inside the projector launch
     lp = calculate_log_prob_M_given_R(output_sample.permute(0, 2, 3, 1), mask.repeat(ns, 1), proj_sample.repeat(ns, 1, 1),
                                       poisson_noise_multiplier, sqrt_reg, theta=theta, angles_i=angles_i, pad=pad,
-                                      reduce="per_object", model=model)
+                                      reduce="per_object", model=model, noise=noise)
     # :305-306 reduce_sum(..., axis=[0, 1, 2]) of the squeezed [B][A][P] and [B][X][Y] tensors: the log-likelihood of a
     # sample is ONE number for the whole batch (the batch axis is summed too), the KL below is per object; :329-330 then
     # broadcast-subtract, and train_step takes the mean over the batch -- i.e. mean_b(KL_b) - sum_b(loglik_b).
@@ -325,6 +325,8 @@ class PVAETrainer:
                 torch.distributed.broadcast(p.data, 0)
         self.params = list(self.enc.parameters()) + list(self.dec.parameters())
         self._bucket = None   # the gradients' resident flat bucket (built on the first step)
+        if getattr(a, "noise", "gaussian") == "poisson" and a.train_pnm:
+            raise ValueError("--noise poisson takes the noise multiplier as data: it cannot be combined with --train_pnm")
         self.pnm = torch.tensor(float(a.pnm), device=device, requires_grad=bool(a.train_pnm))
         # fused: the whole Adam update in one multi-tensor launch on the device (the default foreach form is ~10)
         self.opt = torch.optim.Adam(self.params + ([self.pnm] if a.train_pnm else []), lr=a.lr, eps=a.adam_epsilon,
@@ -414,7 +416,7 @@ class PVAETrainer:
                                                       self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
                                                       theta=self.theta_host, angles_i=angles_i, pad=self.pad,
                                                       deterministic=a.deterministic, use_normal=a.use_normal,
-                                                      model=getattr(a, "model", "rotate"))
+                                                      model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"))
         # ctvae/main_ct_vae.py:478 reduce_mean(loss_M_VAE) / 1e5 = mean_b(KL term) - loglik, where loglik already sums
         # over the batch.  Written so that the ranks' losses ADD UP to the global one (gradients are summed over ranks):
         # each rank contributes its objects' KL / global_B and its own objects' log-likelihood.
@@ -536,7 +538,7 @@ class PVAETrainer:
                                                         self.dec, self.pnm, self.sqrt_reg, self.kl_anneal, a.klm,
                                                         num_samples=a.ns, theta=self.theta_host, angles_i=None, pad=self.pad,
                                                         deterministic=a.deterministic, use_normal=a.use_normal,
-                                                        model=getattr(a, "model", "rotate"))
+                                                        model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"))
             losses.append(loss_vec.mean() / 1e5)
             recons.append(recon.permute(0, 2, 3, 1))
         loss_final = torch.stack(losses).cpu().numpy()
@@ -577,6 +579,9 @@ def get_args(argv=None):
     p.add_argument("--model", choices=["rotate", "siddon"], default="rotate",
                    help="forward model of the likelihood term: the reference's rotate-and-sum, or the ray-driven projector the "
                         "datasets are made with (tomopy.project)")
+    p.add_argument("--noise", choices=["gaussian", "poisson"], default="gaussian",
+                   help="noise model of the likelihood term: the reference's Gaussian approximation Normal(loc, sqrt(loc / pnm)), or "
+                        "the exact Poisson law the measurements are drawn from (not with --train_pnm)")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")

@@ -57,6 +57,8 @@ extern "C" {
 #define CTPVAE_EHIP (-2)     /* a HIP runtime call failed */
 #define CTPVAE_ENODEV (-3)   /* no gfx950 device visible */
 
+#define CTPVAE_NOISE_GAUSSIAN 0 /* the likelihood's noise model: Normal(loc, eps + sqrt(loc / pnm + eps)), ctpvae_loglik_fwd_f32 */
+#define CTPVAE_NOISE_POISSON 1  /* the exact Poisson(loc * pnm) of ctpvae_poisson_loglik_fwd_f32 */
 #define CTPVAE_NEAREST 0     /* tfa.image.rotate default, project_tf_fast */
 #define CTPVAE_BILINEAR 1    /* project_tf_low_mem */
 
@@ -284,6 +286,15 @@ int ctpvae_rotate_fwd_compact_f32(const float *img_dev, int S, int H, int W, int
                                   const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
                                   const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, float *sino_dev,
                                   float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev, ctpvae_stream_t stream);
+/* The same call with the likelihood's noise model as an operand (added at ABI 3400): noise = CTPVAE_NOISE_GAUSSIAN is the call
+ * above, bit for bit; CTPVAE_NOISE_POISSON stores / reduces the exact Poisson log-probability of ctpvae_poisson_loglik_fwd_f32 (its
+ * bits) and, in dlp_dev, d lp / d ray-sum as ctpvae_poisson_loglik_bwd_f32 forms it -- the operand of the unchanged scaled backward.
+ * eps is ignored under POISSON; the per-object sums keep their fixed order.  Without lp_dev / lp_sum_dev noise selects nothing. */
+int ctpvae_rotate_fwd_compact_noise_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *cplan_dev,
+                                        const int *angle_idx, int n_idx, int idx_on_host, const float *mask_dev,
+                                        const float *meas_dev, int dense_inputs, const float *pnm_dev, float eps, int noise,
+                                        float *sino_dev, float *lp_dev, float *dlp_dev, float *lp_part_dev, float *lp_sum_dev,
+                                        ctpvae_stream_t stream);
 
 /* ... and the TF_COMPAT / NEAREST backward of such a subset: gsino_dev [S][n_idx][PW], Tinv8_dev the DENSE inverted table
  * [A_plan][8]; row k of a cotangent uses table row angle_idx_dev[k].  Same bits as ctpvae_rotate_bwd_scaled_f32 on the
@@ -432,6 +443,13 @@ int ctpvae_siddon_fwd_loglik_f32(const float *obj_dev, int oy, int ox, int oz, c
                                  const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
                                  const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
                                  void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev, ctpvae_stream_t stream);
+/* _fwd_loglik with the noise model as an operand (CTPVAE_NOISE_GAUSSIAN: the call above, bit for bit; CTPVAE_NOISE_POISSON: the
+ * expressions of ctpvae_poisson_loglik_fwd_f32 / _bwd_f32 on every ray-sum, eps ignored).  _bwd_sel_scaled serves both. */
+int ctpvae_siddon_fwd_loglik_noise_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                       const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                       const float *mask_dev, const float *meas_dev, int dense, const float *pnm_dev, float eps,
+                                       int noise, void *workspace_dev, float *sino_dev, float *lp_dev, float *dlp_dev,
+                                       ctpvae_stream_t stream);
 int ctpvae_siddon_bwd_sel_scaled_f32(const float *data_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                                      const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
                                      const void *workspace_dev, const float *scale_dev, long long scale_stride, float *recon_dev,
@@ -526,6 +544,27 @@ int ctpvae_loglik_fwd_f32(const float *proj_dev, const float *mask_dev, const fl
 int ctpvae_loglik_bwd_f32(const float *proj_dev, const float *mask_dev, const float *x_dev,
                           const float *gout_dev, int B, int A, int P, const float *pnm_dev, float eps,
                           float *gproj_dev, float *gpnm_dev, ctpvae_stream_t stream);
+
+/* ---- a8, noise = poisson: the exact model of the measurements (ctvae/toy_mcmc_v2_functions.py:30-64,
+ * tfd.Poisson(proj * mask * pnm, force_probs_to_zero_outside_support=False).log_prob(x * pnm); TFP 0.14 Poisson._log_prob).
+ * Shapes as above.  With k = x * pnm and lam = (proj * mask) * pnm:
+ *   out = multiply_no_nan(log lam, k) - lgamma(k + 1) - lam
+ * evaluated in fp32 as  k (log1p(u) - u) - r(k),  u = (lam - k) / k,  r(k) = lgamma(k + 1) - (k log k - k)  (the Stirling
+ * remainder: 0.5 log(2 pi k) + 1/12k - 1/360k^3 + 1/1260k^5 from k = 8 on, lgammaf below) -- the textbook form's three terms are
+ * 1e5 .. 1e7 at pnm = 1e4 and cancel to a value of order 1 .. 10 (max error against float64 on 200,000 draws from the model: 0.09;
+ * this form: 2.0e-6 / 1.3e-5 / 1.0e-4 at pnm 1 / 1e2 / 1e4).  What is left is not r(k) but the rounding of lam and k themselves,
+ * ~ 2^-23 |k - lam|, and the cancellation in log1p(u) - u at small u.
+ *   k == 0:           out = -lam; lam == 0 and k == 0 (a masked-out angle: mask and measurement are 0): out = 0
+ *   lam == 0, k > 0:  out = -inf          lam < 0: NaN, as TFP; nothing traps          k < 0: -inf (outside the support)
+ *   k need not be an integer.
+ * bwd: gproj = gout * mask * pnm * (k - lam) / lam; k == 0: gout * (-mask * pnm), so 0 at a masked angle.  The derivative is that
+ * of the formula wherever the formula can be differentiated, as TFP's autograd gives it: it stays finite where out is NaN
+ * (lam < 0: d log lam = 1 / lam) or -inf (k < 0), and is +inf at lam == 0, k > 0.  pnm is DATA in this
+ * model: there is no d / d pnm.  Parity with TFP's own bits is not pinned (different log / lgamma implementations). */
+int ctpvae_poisson_loglik_fwd_f32(const float *proj_dev, const float *mask_dev, const float *x_dev, int B, int A, int P,
+                                  const float *pnm_dev, float *out_dev, ctpvae_stream_t stream);
+int ctpvae_poisson_loglik_bwd_f32(const float *proj_dev, const float *mask_dev, const float *x_dev, const float *gout_dev,
+                                  int B, int A, int P, const float *pnm_dev, float *gproj_dev, ctpvae_stream_t stream);
 
 /* ---- f2: sparse noisy measurements (the step that feeds the training loop) -------------------------------------
  * ctvae/create_masks.py:80-103 in one launch: out[s][a][j] = Poisson(max(sino[s][a][j], 0) * mask[s][a] * pnm) / pnm.
