@@ -20,6 +20,12 @@
 // The training call on this projector (calculate_log_prob_M_given_R(model="siddon"), ctvae/helper_functions.py:336-368): the
 // forward kernels' LIKELIHOOD store (SidLogLik: log-probability and d lp / d ray-sum of every ray-sum, loglik_math.h) and the
 // gather's scaled store, both with the step's angle subset as an index operand into the dense geometry's tables.
+// MLEM / OSEM (tomopy.recon(algorithm = 'mlem' | 'osem'), recon.py _mlem; libtomo mlem.c / osem.c restated [3P-recalled: TomoPy
+// 1.11.0]): the forward kernels' RATIO store (meas / A x) and the gather's MULTIPLY store (x *= A_sel^T ratio / sum_dist), both over
+// an angle subset of the dense geometry -- an iteration of a block is these two launches.  ONE DEVIATION from libtomo, which skips
+// only rays without segments and divides by a ray-sum of 0 on rays that do cross pixels (inf / NaN: an OSEM block that drives the
+// pixels outside the object to exactly 0 makes the next block's 0 / 0 spread over the whole image): the ratio of a ray whose
+// ray-sum is 0 is stored as 0.  On rays without segments the two rules agree (their ray-sum is 0).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -205,7 +211,8 @@ struct SidLogLik {
     {
         SidLogLik r = *this;
         const size_t o = s0 * n_rows * dx, sa = s0 * (dense ? dt_all : n_rows);
-        r.mask += sa, r.meas += sa * dx, r.lp += o;
+        if (mask) r.mask += sa;
+        r.meas += sa * dx, r.lp += o;
         if (sino) r.sino += o;
         if (dlp) r.dlp += o;
         return r;
@@ -225,6 +232,18 @@ __device__ __forceinline__ void siddon_loglik_store(const SidLogLik &ll, const S
     if (ll.sino) ll.sino[o] = sim;
     LogLikEpilogue ep{ll.mask, ll.meas, ll.pnm, ll.eps, ll.lp, ll.dlp};
     ep.template write<NOISE>(o, sa * g.dx + d, sa, sim);
+}
+// The ratio store of the forward kernels (MLEM / OSEM; kernels of their own names with NOISE = kSidStoreRatio, operands in a
+// SidLogLik: sel / dt_all as above, meas always dense, lp = the output): ratio = meas / sim where sim != 0, else 0 -- libtomo's
+// mlem.c divides wherever the ray has segments; the guard is the build's one deviation (see the head of this file).
+constexpr int kSidStoreRatio = 2;
+// (it travels in the host dispatch's `noise` argument beside the public noise models: it must never be one of them)
+static_assert(kSidStoreRatio != CTPVAE_NOISE_GAUSSIAN && kSidStoreRatio != CTPVAE_NOISE_POISSON && kSidStoreRatio > CTPVAE_NOISE_POISSON,
+              "the ratio store's selector collides with a CTPVAE_NOISE_* value");
+__device__ __forceinline__ void siddon_ratio_store(const SidLogLik &ll, const SidGeom &g, int sl, int k, int pa, int d, float sim)
+{
+    const float m = ll.meas[((size_t)sl * ll.dt_all + pa) * g.dx + d];
+    ll.lp[((size_t)sl * g.dt + k) * g.dx + d] = sim != 0.0f ? m / sim : 0.0f;
 }
 typedef float sid_f32x2 __attribute__((ext_vector_type(2)));
 template <int NS> struct SidVec { typedef float type; };
@@ -274,7 +293,9 @@ __device__ __forceinline__ void siddon_fwd_body(const float *obj, SidGeom g, con
             acc += m * dist;
         });
         auto store = [&](int sl, float sim) {
-            if constexpr (LL) {
+            if constexpr (LL && NOISE == kSidStoreRatio) {
+                siddon_ratio_store(ll, g, sl, p, pa, d, sim);
+            } else if constexpr (LL) {
                 siddon_loglik_store<NOISE>(ll, g, sl, p, pa, d, sim);
             } else {
                 const size_t o = ((size_t)sl * g.dt + p) * g.dx + d;
@@ -309,6 +330,16 @@ __global__ __launch_bounds__(1024) void siddon_fwd_poisson_kernel(const float *_
                                                                  int mode, float *__restrict__ data, SidLogLik ll)
 {
     siddon_fwd_body<USE_LDS, NS, true, 1>(obj, g, sin_t, cos_t, quad_t, p_per_blk, meas, rn2, mode, data, ll);
+}
+template <bool USE_LDS, int NS>
+__global__ __launch_bounds__(1024) void siddon_fwd_ratio_kernel(const float *__restrict__ obj, SidGeom g,
+                                                               const float *__restrict__ sin_t,
+                                                               const float *__restrict__ cos_t,
+                                                               const int *__restrict__ quad_t, int p_per_blk,
+                                                               const float *__restrict__ meas, const float *__restrict__ rn2,
+                                                               int mode, float *__restrict__ data, SidLogLik ll)
+{
+    siddon_fwd_body<USE_LDS, NS, true, kSidStoreRatio>(obj, g, sin_t, cos_t, quad_t, p_per_blk, meas, rn2, mode, data, ll);
 }
 
 // Many slices per walk, from global memory: a grid too large for a PAIR of slices in LDS (184 x 184: the reconstruction grid of
@@ -367,6 +398,43 @@ __global__ __launch_bounds__(256) void siddon_fwd_packed_kernel(const float *__r
             const size_t o = ((size_t)(s0 + k) * g.dt + p) * g.dx + d;
             data[o] = siddon_fwd_store(mode, sim, meas, rn2, data, o, (size_t)p * g.dx + d);
         }
+    }
+}
+// The packed walk with the ratio store (MLEM / OSEM): the kernel above, statement for statement, up to its store -- a twin of its
+// own rather than a shared body, because inlining the walk through one changed the register allocation of the existing
+// instantiations (profiles/r11_mlem.txt, section 2), and those keep their code.
+template <int NS>
+__global__ __launch_bounds__(256) void siddon_fwd_packed_ratio_kernel(const float *__restrict__ packed, SidGeom g,
+                                                                     const float *__restrict__ sin_t,
+                                                                     const float *__restrict__ cos_t,
+                                                                     const int *__restrict__ quad_t, SidLogLik ll)
+{
+    const int grp = blockIdx.y, s0 = grp * NS;
+    const int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= g.dt * g.dx) return;
+    const int p = ray / g.dx, d = ray - p * g.dx;
+    const int pa = siddon_sel_angle(ll.sel, p, ll.dt_all);
+    const int oz = g.oz;
+    const float4 *img = reinterpret_cast<const float4 *>(packed + (size_t)grp * g.ox * g.oz * NS);
+    float acc[NS], pm[NS], pd = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NS; ++k) acc[k] = 0.0f, pm[k] = 0.0f;
+    siddon_walk_ray(g, sin_t[pa], cos_t[pa], quad_t[pa], d, [&](int ix, int iy, float dist) {
+#pragma unroll
+        for (int k = 0; k < NS; ++k) acc[k] += pm[k] * pd;       // the previous segment (0 + 0 * 0 the first time)
+        const float4 *q = img + (size_t)(ix * oz + iy) * (NS / 4);
+#pragma unroll
+        for (int k = 0; k < NS / 4; ++k) {
+            const float4 v = q[k];
+            pm[4 * k] = v.x, pm[4 * k + 1] = v.y, pm[4 * k + 2] = v.z, pm[4 * k + 3] = v.w;
+        }
+        pd = dist;
+    });
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+        const float sim = acc[k] + pm[k] * pd;
+        if (s0 + k >= g.oy) break;
+        siddon_ratio_store(ll, g, s0 + k, p, pa, d, sim);
     }
 }
 
@@ -698,6 +766,8 @@ __device__ __forceinline__ void tv_dual_q(const TvPrimal &t, const float *xb, co
 
 // EPI 0: recon = A^T data.   EPI 1 (SIRT): recon += (A^T data) / colsum where colsum != 0 (libtomo sirt.c's last loop).
 // EPI 3 (the training call's backward): recon[s] = scale[s] * (A_sel^T data[s]) over an angle subset of the dense geometry (SidSel).
+// EPI 4 (MLEM / OSEM, libtomo mlem.c's last loop): recon *= (A_sel^T data) / colsum where colsum != 0, in place, over an angle
+// subset as in EPI 3 (colsum: the block's sum_dist = A_sel^T 1).
 template <int NS, int EPI>
 __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     const float *__restrict__ data, SidGeom g, const float *__restrict__ sin_t, const float *__restrict__ cos_t,
@@ -705,7 +775,7 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     const int *__restrict__ degen_angle, const float *__restrict__ D, const float *__restrict__ colsum, int CH, float tau,
     float *__restrict__ recon, TvPrimal tv, SidSel ss)
 {
-    constexpr bool SEL = EPI == 3;
+    constexpr bool SEL = EPI == 3 || EPI == 4;
     auto angle_of = [&](int k) { return SEL ? siddon_sel_angle(ss.sel, k, ss.dt_all) : k; };
     extern __shared__ float lds[];
     // LDS: lines [CH][SEG] float4 | vals [NS][kGatherPlane] | seg_lo [CH] | live [CH] | anyD
@@ -828,6 +898,9 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
             if (cs != 0.0f) *out += acc[k] / cs;
         } else if constexpr (EPI == 3) {
             *out = ss.scale ? ss.scale[(size_t)(s0 + k) * ss.scale_stride] * acc[k] : acc[k];
+        } else if constexpr (EPI == 4) {
+            const float cs = colsum[ix * g.oz + iy];
+            if (cs != 0.0f) *out = *out * (acc[k] / cs);
         } else {   // EPI 2: the TV stand-in's primal step (TvPrimal above); `recon` is not written
             const size_t so = (size_t)(s0 + k) * npix, c = (size_t)ix * g.oz + iy;
             const float *xb = tv.xbar_in + so, *qxi = tv.qx_in + so, *qyi = tv.qy_in + so;
@@ -950,14 +1023,17 @@ long long ctpvae_siddon_fwd_workspace_bytes(int oy, int ox, int oz)
 template <int NS>
 static int siddon_fwd_packed(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                              const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev,
-                             int mode, float *packed, float *data_dev, hipStream_t stream, const SidLogLik *ll)
+                             int mode, float *packed, float *data_dev, hipStream_t stream, const SidLogLik *ll, int noise)
 {
     const int npix = ox * oz, groups = ceil_div(oy, NS);
     CTPVAE_REQUIRE(groups <= 65535, "siddon_fwd: at most %d slices per call with a workspace (got %d)", 65535 * NS, oy);
     hipLaunchKernelGGL(siddon_pack_kernel<NS>, dim3(ceil_div(npix, 256), groups), dim3(256), 0, stream, obj_dev, oy, npix, packed);
     CTPVAE_LAUNCH_CHECK("siddon_pack_kernel");
     const SidGeom g{oy, ox, oz, dt, dx, siddon_mov(dx, center)};
-    if (ll)
+    if (ll && noise == kSidStoreRatio)
+        hipLaunchKernelGGL(siddon_fwd_packed_ratio_kernel<NS>, dim3(ceil_div(dt * dx, 256), groups), dim3(256), 0, stream, packed, g,
+                           sin_dev, cos_dev, quad_dev, *ll);
+    else if (ll)
         hipLaunchKernelGGL((siddon_fwd_packed_kernel<NS, true>), dim3(ceil_div(dt * dx, 256), groups), dim3(256), 0, stream, packed, g,
                            sin_dev, cos_dev, quad_dev, meas_dev, rn2_dev, mode, data_dev, *ll);
     else
@@ -992,9 +1068,9 @@ static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const flo
     CTPVAE_REQUIRE(workspace_dev, "siddon_fwd: %d slices need the workspace", oy);
     CTPVAE_REQUIRE(((uintptr_t)workspace_dev & 15) == 0, "siddon_fwd: the workspace must be 16-byte aligned");
     return ns == 8 ? siddon_fwd_packed<8>(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode,
-                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll)
+                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll, noise)
                    : siddon_fwd_packed<4>(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode,
-                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll);
+                                          (float *)workspace_dev, data_dev, (hipStream_t)stream, ll, noise);
 }
 
 int ctpvae_siddon_fwd_ws_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
@@ -1059,6 +1135,10 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
         CTPVAE_LAUNCH_CHECK("siddon_fwd_kernel");
         return CTPVAE_OK;
     };
+    if (ll && noise == kSidStoreRatio) {
+        if (!use_lds) return launch(siddon_fwd_ratio_kernel<false, 1>, 0);
+        return ns == 2 ? launch(siddon_fwd_ratio_kernel<true, 2>, lds_bytes) : launch(siddon_fwd_ratio_kernel<true, 1>, lds_bytes);
+    }
     if (ll && noise == CTPVAE_NOISE_POISSON) {
         if (!use_lds) return launch(siddon_fwd_poisson_kernel<false, 1>, 0);
         return ns == 2 ? launch(siddon_fwd_poisson_kernel<true, 2>, lds_bytes) : launch(siddon_fwd_poisson_kernel<true, 1>, lds_bytes);
@@ -1106,6 +1186,22 @@ int ctpvae_siddon_fwd_loglik_noise_f32(const float *obj_dev, int oy, int ox, int
 {
     return siddon_fwd_loglik(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt_all, dx, center, sel_dev, n_sel, mask_dev, meas_dev,
                              dense, pnm_dev, eps, noise, workspace_dev, sino_dev, lp_dev, dlp_dev, stream);
+}
+
+// MLEM / OSEM's forward (recon.py _mlem): see the header.
+int ctpvae_siddon_fwd_ratio_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                const float *meas_dev, void *workspace_dev, float *ratio_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(obj_dev && sin_dev && cos_dev && quad_dev && meas_dev && ratio_dev, "siddon_fwd_ratio: null pointer");
+    CTPVAE_REQUIRE(oy >= 0 && ox > 0 && oz > 0 && dt_all > 0 && dx > 0,
+                   "siddon_fwd_ratio: bad sizes (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox, oz, dt_all, dx);
+    CTPVAE_REQUIRE(sel_dev ? n_sel > 0 : (n_sel == dt_all || n_sel == 0),
+                   "siddon_fwd_ratio: n_sel must be positive with sel_dev, and 0 or dt_all without (got %d, dt_all=%d)", n_sel, dt_all);
+    if (oy == 0) return CTPVAE_OK;
+    const SidLogLik ll{sel_dev, dt_all, nullptr, meas_dev, nullptr, 0.0f, 1, nullptr, ratio_dev, nullptr};
+    return siddon_fwd_ws(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, nullptr, nullptr, 0,
+                         workspace_dev, nullptr, stream, &ll, kSidStoreRatio);
 }
 
 // ---- back-projector (transpose) and SIRT row weights -----------------------------------------------------------
@@ -1191,7 +1287,7 @@ static int siddon_gather_launch(const float *data, const SidGeom &g, const float
         CTPVAE_LAUNCH_CHECK("siddon_bwd_gather_kernel");
         return CTPVAE_OK;
     };
-    if (ss) return launch(siddon_bwd_gather_kernel<NS, 3>);
+    if (ss) return colsum ? launch(siddon_bwd_gather_kernel<NS, 4>) : launch(siddon_bwd_gather_kernel<NS, 3>);
     if (tv) return launch(siddon_bwd_gather_kernel<NS, 2>);
     return colsum ? launch(siddon_bwd_gather_kernel<NS, 1>) : launch(siddon_bwd_gather_kernel<NS, 0>);
 }
@@ -1275,6 +1371,22 @@ int ctpvae_siddon_bwd_sel_scaled_f32(const float *data_dev, int oy, int ox, int 
     const SidSel ss{sel_dev, dt_all, scale_dev, scale_stride};
     return siddon_bwd_prepared(data_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, workspace_dev,
                                nullptr, recon_dev, stream, nullptr, &ss);
+}
+
+// MLEM / OSEM's update (recon.py _mlem): see the header.
+int ctpvae_siddon_bwd_sel_mul_f32(const float *ratio_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                  const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                  const void *workspace_dev, const float *colsum_dev, float *x_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(ratio_dev && sin_dev && cos_dev && quad_dev && workspace_dev && colsum_dev && x_dev, "siddon_bwd_sel_mul: null pointer");
+    CTPVAE_REQUIRE(oy >= 0 && ox > 0 && oz > 0 && dt_all > 0 && dx > 0,
+                   "siddon_bwd_sel_mul: bad sizes (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox, oz, dt_all, dx);
+    CTPVAE_REQUIRE(sel_dev ? n_sel > 0 : (n_sel == dt_all || n_sel == 0),
+                   "siddon_bwd_sel_mul: n_sel must be positive with sel_dev, and 0 or dt_all without (got %d, dt_all=%d)", n_sel, dt_all);
+    if (oy == 0) return CTPVAE_OK;
+    const SidSel ss{sel_dev, dt_all, nullptr, 0};
+    return siddon_bwd_prepared(ratio_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, workspace_dev,
+                               colsum_dev, x_dev, stream, nullptr, &ss);
 }
 
 // Round 4: the TV stand-in's primal step as the back-projector's store (TvPrimal above; recon.py _tv).  p_dev [oy][dt][dx] the dual

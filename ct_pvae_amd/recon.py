@@ -5,7 +5,8 @@ The reference makes the encoder's input channels with TomoPy on the CPU (ctvae/h
     tomopy.recon(proj_sample_expand, theta, center=None, sinogram_order=True, algorithm=algorithm)       # :503, per algorithm
     tomopy.recon(mask_expand, theta, center=None, sinogram_order=True, algorithm='fbp', filter_name='none')   # :514
 
-with `algorithm` one of 'gridrec' (the default, ctvae/main_ct_vae.py:111-112), 'sirt', 'tv', 'fbp' (README.md:80,221).
+with `algorithm` one of 'gridrec' (the default, ctvae/main_ct_vae.py:111-112), 'sirt', 'tv', 'fbp' (README.md:80,221) -- any
+tomopy name passes through --algorithms and evaluate_sinogram(algorithm=...), so the Poisson estimators 'mlem' and 'osem' are here too.
 Here `recon` takes the same arguments and runs on the hand-written kernels behind include/ctpvae_radon.h:
 
     'fbp'      libtomo's fbp.c: the ray-driven back-projection of the sinogram = the TRANSPOSE of tomopy.project
@@ -20,6 +21,17 @@ Here `recon` takes the same arguments and runs on the hand-written kernels behin
                'shepp', 'cosine', 'hann', 'hamming', 'ramlak', 'butterworth' are built too.  [3P-recalled: TomoPy 1.11.0]
                (The round-2 stand-in -- float64 ramp-filtered back-projection on the same grid -- stays reachable under its own
                name: algorithm='fbp', filter_name='ramp'; it is NOT a tomopy filter name.)
+    'mlem'     libtomo's mlem.c on the same operator pair, the maximum-likelihood estimate under the Poisson model the data are
+               simulated with: per iteration  sim = A x;  ratio = data / sim;  x *= (A^T ratio) / sum_dist  (sum_dist = A^T 1),
+               tomopy's defaults num_iter=1, init 1e-6.  An iteration is TWO launches: the forward's store is the ratio
+               (ctpvae_siddon_fwd_ratio_f32), the back-projector's store is the multiplicative update (ctpvae_siddon_bwd_sel_mul_f32).
+               ONE DEVIATION: libtomo skips only rays without segments and divides by sim == 0 on rays that do cross pixels (inf /
+               NaN); here the ratio is 0 wherever sim == 0.  On rays without segments the two rules agree.  [3P-recalled: TomoPy 1.11.0]
+    'osem'     libtomo's osem.c: mlem over num_block (default 1) ordered subsets of the angles, block b = ind_block[b * (dt //
+               num_block) : ...] (default arange(dt)), the last block taking the remainder; blocks run in order inside every iteration
+               and x is updated after each with the block's own sum_dist.  The subsets are index operands into ONE prepared geometry;
+               num_block=1 gives mlem's bits.  Same deviation: without it a block that drives the pixels outside the object to
+               exactly 0 makes the next block's 0 / 0 spread over the whole image.  [3P-recalled: TomoPy 1.11.0]
     'tv'       STAND-IN, flagged: total-variation regularised reconstruction on the same operator pair by the diagonally
                preconditioned Chambolle-Pock iteration (Pock & Chambolle 2011: step sizes from the operator's own row and
                column sums -- sirt.c's sum_dist2-free weights -- so nothing has to be tuned), reg_par[0] = the TV weight.
@@ -42,7 +54,7 @@ from .helper_functions import _siddon_forward, _siddon_tables
 
 __all__ = ["recon", "siddon_backproject", "crop", "evaluate_sinogram", "ALGORITHMS", "GRIDREC_FILTERS"]
 
-ALGORITHMS = ("fbp", "sirt", "gridrec", "tv")
+ALGORITHMS = ("fbp", "sirt", "gridrec", "tv", "mlem", "osem")
 GRIDREC_FILTERS = {"none": 0, "shepp": 1, "cosine": 2, "hann": 3, "hamming": 4, "ramlak": 5, "parzen": 6, "butterworth": 7}
 # tomopy/recon/algorithm.py _get_algorithm_kwargs [3P-recalled]: the default filter_name is per algorithm
 _DEFAULT_FILTER = {"gridrec": "parzen", "fbp": "none"}
@@ -164,6 +176,55 @@ def _sirt(data, tables, gx, gy, num_iter, init):
     return x
 
 
+def _osem_blocks(dt, num_block, ind_block):
+    """osem.c's subsets: block b = ind_block[b * (dt // num_block) : (b + 1) * (dt // num_block)], the last one to the end."""
+    nb = 1 if num_block is None else int(num_block)
+    if nb < 1 or nb > dt:
+        raise ValueError(f"recon: num_block must be in 1 .. the number of angles ({dt}), got {num_block!r}")
+    ind = np.arange(dt) if ind_block is None else np.asarray(ind_block)
+    if ind.ndim != 1 or ind.size != dt or ind.dtype.kind not in "iu" or ind.min() < 0 or ind.max() >= dt:
+        raise ValueError(f"recon: ind_block must hold {dt} integer indices into theta (0 .. {dt - 1})")
+    step = dt // nb
+    return [np.ascontiguousarray(ind[b * step:(b + 1) * step if b < nb - 1 else dt], dtype=np.int32) for b in range(nb)]
+
+
+def _mlem(data, tables, gx, gy, num_iter, init, blocks):
+    """libtomo mlem.c / osem.c: per block and iteration ONE forward launch (its store is the ratio data / A x, 0 where A x == 0)
+    and ONE back-projector launch (its store is x *= A_b^T ratio / sum_dist).  blocks: int32 index vectors into the angles (None:
+    all of them, in order), uploaded once and used as `sel` operands of one prepared geometry; a block's sum_dist = A_b^T 1 is
+    geometry, computed once."""
+    lib = _lib.load()
+    sin_t, cos_t, quad = tables
+    oy, dt, dx = data.shape
+    dev = data.device
+    center, sp = ctypes.c_float(dx / 2.0), _stream_ptr()
+    geo = (gx, gy, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), dt, dx, center)
+    ws = _bp_workspace(tables, oy, gx, gy, dt, dx, dev)
+    need = lib.ctpvae_siddon_fwd_workspace_bytes(oy, gx, gy)
+    _lib.check(need, "siddon_fwd_workspace_bytes")
+    fws = torch.empty(int(need), dtype=torch.uint8, device=dev) if need else None
+    ones = torch.ones((1, dt, dx), dtype=torch.float32, device=dev)
+    plan = []
+    for b in blocks:
+        sel = None if b is None else torch.from_numpy(b).to(dev)
+        n = dt if b is None else int(b.size)
+        colsum = _fwd._new_output((1, gx, gy), torch.float32, dev)                        # sum_dist of the block
+        _lib.check(lib.ctpvae_siddon_bwd_sel_scaled_f32(ones.data_ptr(), 1, *geo, sel.data_ptr() if sel is not None else None, n,
+                                                        ws.data_ptr(), None, 0, colsum.data_ptr(), sp), "siddon_bwd_sel_scaled")
+        plan.append((sel, n, colsum))
+    x = init.contiguous().clone()
+    ratio = _fwd._new_output((oy * max(n for _, n, _ in plan) * dx,), torch.float32, dev)   # a block uses its first oy * n * dx
+    for _ in range(int(num_iter)):
+        for sel, n, colsum in plan:
+            selp = sel.data_ptr() if sel is not None else None
+            _lib.check(lib.ctpvae_siddon_fwd_ratio_f32(x.data_ptr(), oy, *geo, selp, n, data.data_ptr(),
+                                                       fws.data_ptr() if fws is not None else None, ratio.data_ptr(), sp),
+                       "siddon_fwd_ratio")
+            _lib.check(lib.ctpvae_siddon_bwd_sel_mul_f32(ratio.data_ptr(), oy, *geo, selp, n, ws.data_ptr(), colsum.data_ptr(),
+                                                         x.data_ptr(), sp), "siddon_bwd_sel_mul")
+    return x
+
+
 _TV_WARNED = False
 
 
@@ -210,12 +271,15 @@ def _tv(data, tables, gx, gy, num_iter, init, lam):
 
 
 def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_recon=None, num_gridx=None, num_gridy=None,
-          num_iter=1, filter_name=None, filter_par=None, reg_par=None, **kwargs):
+          num_iter=1, filter_name=None, filter_par=None, reg_par=None, num_block=None, ind_block=None, **kwargs):
     """tomopy.recon's call shape for the algorithms above.  tomo: [angles][slices][dx] (sinogram_order=False) or
     [slices][angles][dx] (True), a float tensor on a HIP device.  Returns [slices][num_gridx][num_gridy] float32.
-    filter_name None = tomopy's default for the algorithm ('parzen' for gridrec, 'none' for fbp)."""
+    filter_name None = tomopy's default for the algorithm ('parzen' for gridrec, 'none' for fbp).  num_block / ind_block: osem's
+    ordered subsets (tomopy's defaults 1 / arange(angles)); given with another algorithm they are refused."""
     if algorithm not in ALGORITHMS:
         raise ValueError(f"recon: unknown algorithm {algorithm!r}; available: {ALGORITHMS}")
+    if algorithm != "osem" and (num_block is not None or ind_block is not None):
+        raise ValueError(f"recon: num_block / ind_block belong to algorithm='osem' (got algorithm={algorithm!r})")
     if filter_name is None:
         filter_name = _DEFAULT_FILTER.get(algorithm, "none")
     data = _as_device_f32(tomo, "tomo")
@@ -229,6 +293,7 @@ def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_r
     if center is not None and float(center) != dx / 2.0:
         raise NotImplementedError("recon: only center=None (the detector's middle, as every reference call passes) is built")
     gx, gy = int(num_gridx or dx), int(num_gridy or dx)
+    blocks = _osem_blocks(dt, num_block, ind_block) if algorithm == "osem" else [None]
     if oy == 0:
         return data.new_empty((0, gx, gy))
     with torch.cuda.device(data.device):
@@ -253,6 +318,8 @@ def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_r
             if not lam > 0:
                 raise ValueError("recon: reg_par[0] (the TV weight) must be positive")
             return _tv(data, tables, gx, gy, num_iter, init, lam)
+        if algorithm in ("mlem", "osem"):
+            return _mlem(data, tables, gx, gy, num_iter, init, blocks)
         return _sirt(data, tables, gx, gy, num_iter, init)
 
 

@@ -38,6 +38,7 @@
  *                                              ctvae/helper_functions.py:33-38
  *   ctpvae_siddon_bwd_f32 / _rownorm_f32       tomopy.recon(algorithm='fbp' | 'sirt') behind iradon_all / evaluate_sinogram
  *                                              ctvae/helper_functions.py:445-457,503,514
+ *   ctpvae_siddon_fwd_ratio_f32 / _bwd_sel_mul_f32   tomopy.recon(algorithm='mlem' | 'osem') behind the same two callers
  *   ctpvae_gridrec_*                           tomopy.recon(algorithm='gridrec'), the default of iradon_all / evaluate_sinogram
  *                                              ctvae/helper_functions.py:445-457,503; ctvae/main_ct_vae.py:111-112
  *   ctpvae_fbp_filter_f64 / _backproject{,_bwd}_f64   iradon  ctvae/fbp_tensorflow.py:14-75
@@ -454,6 +455,25 @@ int ctpvae_siddon_bwd_sel_scaled_f32(const float *data_dev, int oy, int ox, int 
                                      const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
                                      const void *workspace_dev, const float *scale_dev, long long scale_stride, float *recon_dev,
                                      ctpvae_stream_t stream);
+/* MLEM / OSEM (tomopy.recon(algorithm='mlem' | 'osem'); libtomo mlem.c / osem.c restated [3P-recalled: TomoPy 1.11.0]) as TWO
+ * projector launches per block and iteration, with nothing elementwise in between (ct_pvae_amd/recon.py _mlem):
+ *   _fwd_ratio:    the forward of ctpvae_siddon_fwd_ws_f32 (same dispatch, same workspace rule, same ray-sums) whose store is
+ *       ratio = meas / (A obj) where the ray-sum != 0, else 0.  sel_dev / n_sel / dt_all as in _fwd_loglik: output row k of
+ *       ratio_dev [oy][rows][dx] is table angle sel[k]; meas_dev [oy][dt_all][dx] is always read DENSE, at the table angle, so
+ *       an OSEM block needs no gathered copy of the data.
+ *   _bwd_sel_mul:  x <- x * ((A_sel^T ratio) / colsum) where colsum != 0, else x unchanged, in place: x_dev [oy][ox][oz],
+ *       ratio_dev [oy][rows][dx], colsum_dev [ox][oz] the block's sum_dist = A_sel^T 1 (_bwd_sel_scaled of ones).  The gather
+ *       and the workspace of _bwd_sel_scaled: PREPARED once for the dense tables, a block costs no _prepare; no atomics:
+ *       equal bits run to run and to a call on the gathered tables.
+ * ONE DEVIATION from libtomo: mlem.c skips only rays without segments and divides by a ray-sum of 0 on rays that do cross pixels
+ * (inf / NaN, which an OSEM block that drives the background to exactly 0 does produce); here such a ratio is 0.  On rays
+ * without segments the two rules agree.  oy == 0 returns without a launch; long batches go in chunks. */
+int ctpvae_siddon_fwd_ratio_f32(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                const float *meas_dev, void *workspace_dev, float *ratio_dev, ctpvae_stream_t stream);
+int ctpvae_siddon_bwd_sel_mul_f32(const float *ratio_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                  const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                  const void *workspace_dev, const float *colsum_dev, float *x_dev, ctpvae_stream_t stream);
 /* Round 4: an iteration of the TV STAND-IN of tomopy.recon(algorithm='tv') (README.md:221 of the reference asks for 'tv';
  * libtomo's tv.c is NOT restated -- ct_pvae_amd/recon.py says so on every call) as TWO projector launches instead of ~15 torch
  * ops around them: the diagonally preconditioned Chambolle-Pock iteration for min 1/2 |A x - b|^2 + lam TV(x) on K = (A; grad),
