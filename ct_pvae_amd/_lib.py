@@ -125,6 +125,8 @@ SIGNATURES = {
                                              _vp, _vp]),
     "ctpvae_siddon_bwd_sel_mul_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _c_int, _vp,
                                                _vp, _vp, _vp]),
+    "ctpvae_siddon_bwd_sel_pml_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _c_int, _vp,
+                                               _vp, _c_float, _c_float, _c_int, _vp, _vp, _vp]),
     "ctpvae_siddon_fwd_resid_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp,
                                              _vp]),
     "ctpvae_siddon_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp]),

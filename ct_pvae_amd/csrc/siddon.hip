@@ -26,6 +26,9 @@
 // only rays without segments and divides by a ray-sum of 0 on rays that do cross pixels (inf / NaN: an OSEM block that drives the
 // pixels outside the object to exactly 0 makes the next block's 0 / 0 spread over the whole image): the ratio of a ray whose
 // ray-sum is 0 is stored as 0.  On rays without segments the two rules agree (their ray-sum is 0).
+// Penalized likelihood (tomopy.recon(algorithm = 'pml_quad' | 'pml_hybrid' | 'ospml_quad' | 'ospml_hybrid'), recon.py _pml): the same
+// RATIO forward, and the gather's PML store (PmlStore: the root of De Pierro's surrogate with the 8-neighbour penalty, x read through
+// an LDS tile with a halo) -- an iteration of a block is again two launches.  Its deviation is stated at PmlStore.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -764,18 +767,75 @@ __device__ __forceinline__ void tv_dual_q(const TvPrimal &t, const float *xb, co
     ny = ay / nrm;
 }
 
+// The penalized-likelihood update (recon.py _pml; libtomo pml_quad.c / pml_hybrid.c / ospml_*.c restated [3P-recalled: TomoPy
+// 1.11.0], checked by re-deriving it as De Pierro's separable surrogate) as the back-projector's store.  With u = A_sel^T ratio (the
+// gather's sum), x = x_in[c] and the pixel's up to eight neighbours k_q in libtomo's order, every operation in fp32 in THIS order:
+//   E = -(x * u);  F = 0;  P = 0;  for q, skipping neighbours outside the grid:
+//       r = x - x_in[k_q];  gam = 1 / (1 + fabs(r / delta)) (hybrid; quad: no factor);  t = (two_beta * w_q) * gam;
+//       F += t;  P -= t * (x + x_in[k_q])
+//   G = P + colsum[c];  S = sqrtf(G * G - (8 * E) * F)
+//   x_out[c] = (-2 * E) / (G + S) where G > 0;  (-G + S) / (4 * F) where G <= 0 and F != 0 (libtomo's form of the same root, which
+//              libtomo uses everywhere: it cancels where G > 0 -- the build's flagged deviation);  x where G <= 0 and F == 0
+// w_q: direct neighbours a, diagonal a / sqrt(2), a = 1 / (n_direct + n_diag / sqrt(2)) over the neighbours that exist (libtomo's
+// tables for interior, edge and corner pixels).  Neighbours are read from x_in (Jacobi): x_in != x_out, the caller swaps them.
+struct PmlStore {
+    const float *x_in;
+    float *x_out;
+    float two_beta, delta;
+    int hybrid;
+};
+// the tile's x_in with a one-pixel halo, per slice, staged where the `vals` planes were once the accumulation is over
+constexpr int kPmlPitch = 64 + 2, kPmlPlane = (kGatherRows + 2) * kPmlPitch;
+static_assert(kPmlPlane <= kGatherPlane, "the halo tile of a slice must fit the slice's plane of staged values");
+__device__ __forceinline__ float pml_update(const PmlStore &pm, const float *tile, int wave, int lane, int ix, int iy, int ox, int oz,
+                                            float u, float cs)
+{
+    const int on_edge = (ix == 0 || ix == ox - 1 ? 1 : 0) + (iy == 0 || iy == oz - 1 ? 1 : 0);      // 0 interior, 1 edge, 2 corner
+    const float w_dir = on_edge == 0 ? 0.1464466094f : on_edge == 1 ? 0.2265409197f : 0.3693980625f;
+    const float w_dia = on_edge == 0 ? 0.1035533906f : on_edge == 1 ? 0.1601886205f : 0.2612038750f;
+    const float *ctr = tile + (wave + 1) * kPmlPitch + (lane + 1);
+    const float x = *ctr;
+    const float E = -(x * u);
+    float F = 0.0f, P = 0.0f;
+    auto term = [&](int di, int dj, float w) {
+        if (ix + di < 0 || ix + di >= ox || iy + dj < 0 || iy + dj >= oz) return;
+        const float xk = ctr[di * kPmlPitch + dj];
+        float t = pm.two_beta * w;
+        if (pm.hybrid) t = t * (1.0f / (1.0f + fabsf((x - xk) / pm.delta)));
+        F += t;
+        P -= t * (x + xk);
+    };
+    term(0, 1, w_dir), term(0, -1, w_dir), term(1, 0, w_dir), term(-1, 0, w_dir);
+    term(1, 1, w_dia), term(1, -1, w_dia), term(-1, 1, w_dia), term(-1, -1, w_dia);
+    const float G = P + cs;
+    const float S = sqrtf(G * G - (8.0f * E) * F);
+    if (G > 0.0f) return (-2.0f * E) / (G + S);
+    return F != 0.0f ? (-G + S) / (4.0f * F) : x;
+}
+
+// The operand of the two stores that bring arrays of their own (EPI 2: tv, EPI 5: pm) is ONE kernel argument: a further argument would
+// move the hidden arguments behind it, and with them two immediates in every existing instantiation (profiles/r12_pml.txt).
+union GatherStore {
+    TvPrimal tv;
+    PmlStore pm;
+};
+
 // EPI 0: recon = A^T data.   EPI 1 (SIRT): recon += (A^T data) / colsum where colsum != 0 (libtomo sirt.c's last loop).
 // EPI 3 (the training call's backward): recon[s] = scale[s] * (A_sel^T data[s]) over an angle subset of the dense geometry (SidSel).
 // EPI 4 (MLEM / OSEM, libtomo mlem.c's last loop): recon *= (A_sel^T data) / colsum where colsum != 0, in place, over an angle
 // subset as in EPI 3 (colsum: the block's sum_dist = A_sel^T 1).
+// EPI 5 (pml_* / ospml_*): pm.x_out = the penalized update of pm.x_in (PmlStore above) over an angle subset as in EPI 4; `recon` is
+// not written.  The one store that needs the workgroup again after the accumulation: lanes outside the grid stay for its staging.
 template <int NS, int EPI>
 __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
     const float *__restrict__ data, SidGeom g, const float *__restrict__ sin_t, const float *__restrict__ cos_t,
     const int *__restrict__ quad_t, const float4 *__restrict__ table, const unsigned *__restrict__ flags,
     const int *__restrict__ degen_angle, const float *__restrict__ D, const float *__restrict__ colsum, int CH, float tau,
-    float *__restrict__ recon, TvPrimal tv, SidSel ss)
+    float *__restrict__ recon, GatherStore st, SidSel ss)
 {
-    constexpr bool SEL = EPI == 3 || EPI == 4;
+    [[maybe_unused]] const TvPrimal &tv = st.tv;
+    [[maybe_unused]] const PmlStore &pm = st.pm;
+    constexpr bool SEL = EPI == 3 || EPI == 4 || EPI == 5;
     auto angle_of = [&](int k) { return SEL ? siddon_sel_angle(ss.sel, k, ss.dt_all) : k; };
     extern __shared__ float lds[];
     // LDS: lines [CH][SEG] float4 | vals [NS][kGatherPlane] | seg_lo [CH] | live [CH] | anyD
@@ -886,6 +946,16 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
             }
         }
     }
+    if constexpr (EPI == 5) {
+        __syncthreads();          // the last chunk has been consumed: the planes are free
+        for (int e = threadIdx.x; e < NS * kPmlPlane; e += blockDim.x) {
+            const int k = e / kPmlPlane, t = e - k * kPmlPlane;
+            const int r = t / kPmlPitch, gi = ix0 - 1 + r, gj = iy0 - 1 + (t - r * kPmlPitch);
+            const bool in = s0 + k < g.oy && gi >= 0 && gi < g.ox && gj >= 0 && gj < g.oz;
+            vals[e] = in ? pm.x_in[(size_t)(s0 + k) * npix + gi * g.oz + gj] : 0.0f;
+        }
+        __syncthreads();
+    }
     if (!mine) return;
 #pragma unroll
     for (int k = 0; k < NS; ++k) {
@@ -901,6 +971,9 @@ __global__ __launch_bounds__(kGatherRows * 64) void siddon_bwd_gather_kernel(
         } else if constexpr (EPI == 4) {
             const float cs = colsum[ix * g.oz + iy];
             if (cs != 0.0f) *out = *out * (acc[k] / cs);
+        } else if constexpr (EPI == 5) {
+            pm.x_out[(size_t)(s0 + k) * npix + ix * g.oz + iy] =
+                pml_update(pm, vals + k * kPmlPlane, wave, lane, ix, iy, g.ox, g.oz, acc[k], colsum[ix * g.oz + iy]);
         } else {   // EPI 2: the TV stand-in's primal step (TvPrimal above); `recon` is not written
             const size_t so = (size_t)(s0 + k) * npix, c = (size_t)ix * g.oz + iy;
             const float *xb = tv.xbar_in + so, *qxi = tv.qx_in + so, *qyi = tv.qy_in + so;
@@ -1271,7 +1344,7 @@ template <int NS>
 static int siddon_gather_launch(const float *data, const SidGeom &g, const float *sin_dev, const float *cos_dev,
                                 const int *quad_dev, const float4 *table, const unsigned *flags, const int *degen,
                                 const float *D, const float *colsum, float *recon, hipStream_t stream, const TvPrimal *tv = nullptr,
-                                const SidSel *ss = nullptr)
+                                const SidSel *ss = nullptr, const PmlStore *pm = nullptr)
 {
     // angles per LDS chunk: two staging rounds of the 512 threads, ~50 KB with eight slices -> three workgroups per CU
     int CH = std::max(1, std::min(g.dt, kGatherMaxCh));
@@ -1279,14 +1352,18 @@ static int siddon_gather_launch(const float *data, const SidGeom &g, const float
     const size_t shmem = (size_t)CH * kGatherSeg * 16 + (size_t)NS * kGatherPlane * 4 + (size_t)CH * 8 + 16;
     const float tau = siddon_tau(g.ox, g.oz);
     const dim3 grid(ceil_div(g.ox, kGatherRows) * ceil_div(g.oz, 64), ceil_div(g.oy, NS)), block(kGatherRows * 64);
+    GatherStore st{};
+    if (tv) st.tv = *tv;
+    if (pm) st.pm = *pm;
     auto launch = [&](auto kernel) -> int {
         static std::atomic<unsigned long long> attr_set{0};
         if (shmem > 64 * 1024) CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
         hipLaunchKernelGGL(kernel, grid, block, shmem, stream, data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, D, colsum,
-                           CH, tau, recon, tv ? *tv : TvPrimal{}, ss ? *ss : SidSel{});
+                           CH, tau, recon, st, ss ? *ss : SidSel{});
         CTPVAE_LAUNCH_CHECK("siddon_bwd_gather_kernel");
         return CTPVAE_OK;
     };
+    if (pm) return launch(siddon_bwd_gather_kernel<NS, 5>);
     if (ss) return colsum ? launch(siddon_bwd_gather_kernel<NS, 4>) : launch(siddon_bwd_gather_kernel<NS, 3>);
     if (tv) return launch(siddon_bwd_gather_kernel<NS, 2>);
     return colsum ? launch(siddon_bwd_gather_kernel<NS, 1>) : launch(siddon_bwd_gather_kernel<NS, 0>);
@@ -1297,9 +1374,9 @@ extern "C" {
 static int siddon_bwd_prepared(const float *data_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                                const int *quad_dev, int dt, int dx, float center, const void *workspace_dev,
                                const float *colsum_dev, float *recon_dev, ctpvae_stream_t stream, const TvPrimal *tv,
-                               const SidSel *ss = nullptr)
+                               const SidSel *ss = nullptr, const PmlStore *pm = nullptr)
 {
-    CTPVAE_REQUIRE(data_dev && sin_dev && cos_dev && quad_dev && (recon_dev || tv) && workspace_dev, "siddon_bwd: null pointer");
+    CTPVAE_REQUIRE(data_dev && sin_dev && cos_dev && quad_dev && (recon_dev || tv || pm) && workspace_dev, "siddon_bwd: null pointer");
     CTPVAE_REQUIRE(oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_bwd: sizes must be positive (oy=%d ox=%d oz=%d dt=%d dx=%d)", oy, ox, oz, dt, dx);
     CTPVAE_REQUIRE(((uintptr_t)workspace_dev & 255) == 0, "siddon_bwd: the workspace must be 256-byte aligned");
@@ -1328,6 +1405,9 @@ static int siddon_bwd_prepared(const float *data_dev, int oy, int ox, int oz, co
         SidSel sss{};
         if (ss) sss = SidSel{ss->sel, ss->dt_all, ss->scale ? ss->scale + (size_t)s0 * ss->scale_stride : nullptr, ss->scale_stride};
         const SidSel *ssp = ss ? &sss : nullptr;
+        PmlStore pms{};
+        if (pm) pms = PmlStore{pm->x_in + (size_t)s0 * npix, pm->x_out + (size_t)s0 * npix, pm->two_beta, pm->delta, pm->hybrid};
+        const PmlStore *pmp = pm ? &pms : nullptr;
         if (ss)
             hipLaunchKernelGGL(siddon_bwd_degenerate_kernel<true>, dim3(g.oy), dim3(256), 0, (hipStream_t)stream, data, g, sin_dev, cos_dev,
                                quad_dev, degen, Ds, sss);
@@ -1337,10 +1417,10 @@ static int siddon_bwd_prepared(const float *data_dev, int oy, int ox, int oz, co
         CTPVAE_LAUNCH_CHECK("siddon_bwd_degenerate_kernel");
         int rc;
         switch (ns) {
-        case 8: rc = siddon_gather_launch<8>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
-        case 4: rc = siddon_gather_launch<4>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
-        case 2: rc = siddon_gather_launch<2>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
-        default: rc = siddon_gather_launch<1>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp); break;
+        case 8: rc = siddon_gather_launch<8>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp, pmp); break;
+        case 4: rc = siddon_gather_launch<4>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp, pmp); break;
+        case 2: rc = siddon_gather_launch<2>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp, pmp); break;
+        default: rc = siddon_gather_launch<1>(data, g, sin_dev, cos_dev, quad_dev, table, flags, degen, Ds, colsum_dev, recon, (hipStream_t)stream, tvp, ssp, pmp); break;
         }
         if (rc) return rc;
     }
@@ -1387,6 +1467,30 @@ int ctpvae_siddon_bwd_sel_mul_f32(const float *ratio_dev, int oy, int ox, int oz
     const SidSel ss{sel_dev, dt_all, nullptr, 0};
     return siddon_bwd_prepared(ratio_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, workspace_dev,
                                colsum_dev, x_dev, stream, nullptr, &ss);
+}
+
+// pml_quad / pml_hybrid / ospml_*'s update (recon.py _pml): see the header.
+int ctpvae_siddon_bwd_sel_pml_f32(const float *ratio_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                  const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                  const void *workspace_dev, const float *colsum_dev, float beta, float delta, int hybrid,
+                                  const float *x_in_dev, float *x_out_dev, ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(ratio_dev && sin_dev && cos_dev && quad_dev && workspace_dev && colsum_dev && x_in_dev && x_out_dev,
+                   "siddon_bwd_sel_pml: null pointer");
+    CTPVAE_REQUIRE(x_in_dev != x_out_dev,
+                   "siddon_bwd_sel_pml: x is read at neighbouring pixels -- in and out must be distinct buffers");
+    CTPVAE_REQUIRE(oy >= 0 && ox >= 2 && oz >= 2 && dt_all > 0 && dx > 0,
+                   "siddon_bwd_sel_pml: bad sizes, the penalty needs a grid of at least 2 x 2 (oy=%d ox=%d oz=%d dt_all=%d dx=%d)", oy, ox,
+                   oz, dt_all, dx);
+    CTPVAE_REQUIRE(sel_dev ? n_sel > 0 : (n_sel == dt_all || n_sel == 0),
+                   "siddon_bwd_sel_pml: n_sel must be positive with sel_dev, and 0 or dt_all without (got %d, dt_all=%d)", n_sel, dt_all);
+    CTPVAE_REQUIRE(std::isfinite(beta) && beta >= 0.0f, "siddon_bwd_sel_pml: beta must be finite and not negative");
+    CTPVAE_REQUIRE(!hybrid || delta > 0.0f, "siddon_bwd_sel_pml: the hybrid penalty needs delta > 0");
+    if (oy == 0) return CTPVAE_OK;
+    const SidSel ss{sel_dev, dt_all, nullptr, 0};
+    const PmlStore pm{x_in_dev, x_out_dev, 2.0f * beta, hybrid ? delta : 0.0f, hybrid ? 1 : 0};
+    return siddon_bwd_prepared(ratio_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, sel_dev ? n_sel : dt_all, dx, center, workspace_dev,
+                               colsum_dev, nullptr, stream, nullptr, &ss, &pm);
 }
 
 // Round 4: the TV stand-in's primal step as the back-projector's store (TvPrimal above; recon.py _tv).  p_dev [oy][dt][dx] the dual

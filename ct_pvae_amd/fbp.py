@@ -140,8 +140,8 @@ def iradon_all(all_proj_samples, all_masks, num_proj_pix, theta, algorithms, sqr
     """Initial reconstructions that feed the encoder (ctvae/helper_functions.py:477-529): one channel per entry of
     `algorithms` -- tomopy.recon(proj_sample_expand, theta, center=None, sinogram_order=True, algorithm=...) cropped to
     x_size x y_size (:503-505) -- plus the un-filtered back-projection of the dose mask (algorithm='fbp',
-    filter_name='none', :514-515).  The reconstructions run on the GPU (ct_pvae_amd/recon.py: 'fbp', 'sirt', 'mlem', 'osem' on
-    the TomoPy-style operator pair, 'gridrec' = libtomo's gridrec.c on csrc/gridrec.hip, 'tv' as a flagged
+    filter_name='none', :514-515).  The reconstructions run on the GPU (ct_pvae_amd/recon.py: 'fbp', 'sirt', 'mlem', 'osem',
+    'pml_quad', 'pml_hybrid', 'ospml_quad', 'ospml_hybrid' on the TomoPy-style operator pair, 'gridrec' = libtomo's gridrec.c on csrc/gridrec.hip, 'tv' as a flagged
     Chambolle-Pock stand-in).
     Returns [n][x_size][y_size][len(algorithms) + 1] float32 on the sinograms' device and, like the reference, writes /
     reads ``all_input_encode.npy`` under `save_path`."""

@@ -6,7 +6,8 @@ The reference makes the encoder's input channels with TomoPy on the CPU (ctvae/h
     tomopy.recon(mask_expand, theta, center=None, sinogram_order=True, algorithm='fbp', filter_name='none')   # :514
 
 with `algorithm` one of 'gridrec' (the default, ctvae/main_ct_vae.py:111-112), 'sirt', 'tv', 'fbp' (README.md:80,221) -- any
-tomopy name passes through --algorithms and evaluate_sinogram(algorithm=...), so the Poisson estimators 'mlem' and 'osem' are here too.
+tomopy name passes through --algorithms and evaluate_sinogram(algorithm=...), so the Poisson estimators 'mlem' and 'osem' and their
+penalized versions 'pml_quad', 'pml_hybrid', 'ospml_quad', 'ospml_hybrid' are here too.
 Here `recon` takes the same arguments and runs on the hand-written kernels behind include/ctpvae_radon.h:
 
     'fbp'      libtomo's fbp.c: the ray-driven back-projection of the sinogram = the TRANSPOSE of tomopy.project
@@ -32,6 +33,23 @@ Here `recon` takes the same arguments and runs on the hand-written kernels behin
                and x is updated after each with the block's own sum_dist.  The subsets are index operands into ONE prepared geometry;
                num_block=1 gives mlem's bits.  Same deviation: without it a block that drives the pixels outside the object to
                exactly 0 makes the next block's 0 / 0 spread over the whole image.  [3P-recalled: TomoPy 1.11.0]
+    'pml_quad' libtomo's pml_quad.c: penalized maximum likelihood,  loglik(x) - beta * 1/2 sum_c sum_q w_q (x[c] - x[k_q])^2  over the
+               8 neighbours k_q of every pixel (direct ones weigh a, diagonal ones a / sqrt(2), sum 1; libtomo's tables for interior,
+               edge and corner pixels), maximised by De Pierro's separable surrogate: per iteration mlem's two launches, the back-
+               projector's store now being the positive root of  2 F x^2 + G x + E = 0  per pixel (E = -x A^T ratio, F and G from
+               the neighbours of the iterate the launch started with and sum_dist; ctpvae_siddon_bwd_sel_pml_f32 states every
+               operation), x ping-ponging between two buffers.  reg_par[0] = beta (None: tomopy's ones, beta = 1); beta = 0 is mlem
+               up to rounding.  [3P-recalled: TomoPy 1.11.0 pml_quad.c / pml_hybrid.c / ospml_quad.c / ospml_hybrid.c; the
+               recollection is checked by re-deriving the update as that surrogate, and tests/test_pml_cpu.py checks that the
+               penalized likelihood rises at every iteration]
+               A SECOND DEVIATION beside mlem's guarded ratio, which these four share: where G > 0 the root is taken as
+               (-2 E) / (G + S), S = sqrt(G^2 - 8 E F); libtomo's (-G + S) / (4 F) subtracts two nearly equal numbers there (float32,
+               20 iterations at beta = 0.01, against the same iteration in float64: 8.7e-7 of the image's maximum against 2.6e-4;
+               tests/test_pml_cpu.py).  Where G <= 0 libtomo's form is the stable one and is used.
+    'pml_hybrid'   libtomo's pml_hybrid.c: the same with an edge-preserving penalty, every neighbour's weight multiplied by
+               1 / (1 + |x[c] - x[k_q]| / delta);  reg_par = [beta, delta] (None: ones).
+    'ospml_quad', 'ospml_hybrid'   libtomo's ospml_*.c: the two over osem's ordered subsets (num_block, ind_block); every block updates
+               x with its own sum_dist and the full beta; num_block=1 gives pml_*'s bits.
     'tv'       STAND-IN, flagged: total-variation regularised reconstruction on the same operator pair by the diagonally
                preconditioned Chambolle-Pock iteration (Pock & Chambolle 2011: step sizes from the operator's own row and
                column sums -- sirt.c's sum_dist2-free weights -- so nothing has to be tuned), reg_par[0] = the TV weight.
@@ -54,7 +72,9 @@ from .helper_functions import _siddon_forward, _siddon_tables
 
 __all__ = ["recon", "siddon_backproject", "crop", "evaluate_sinogram", "ALGORITHMS", "GRIDREC_FILTERS"]
 
-ALGORITHMS = ("fbp", "sirt", "gridrec", "tv", "mlem", "osem")
+ALGORITHMS = ("fbp", "sirt", "gridrec", "tv", "mlem", "osem", "pml_quad", "pml_hybrid", "ospml_quad", "ospml_hybrid")
+_PML = ("pml_quad", "pml_hybrid", "ospml_quad", "ospml_hybrid")
+_BLOCKED = ("osem", "ospml_quad", "ospml_hybrid")           # the algorithms that take num_block / ind_block
 GRIDREC_FILTERS = {"none": 0, "shepp": 1, "cosine": 2, "hann": 3, "hamming": 4, "ramlak": 5, "parzen": 6, "butterworth": 7}
 # tomopy/recon/algorithm.py _get_algorithm_kwargs [3P-recalled]: the default filter_name is per algorithm
 _DEFAULT_FILTER = {"gridrec": "parzen", "fbp": "none"}
@@ -225,6 +245,60 @@ def _mlem(data, tables, gx, gy, num_iter, init, blocks):
     return x
 
 
+def _pml_reg_par(algorithm, reg_par):
+    """(beta, delta, hybrid) of a pml_* / ospml_* call: reg_par None = tomopy's ones; a scalar or a sequence gives beta = reg_par[0]
+    and, for the hybrid penalty, delta = reg_par[1]."""
+    hybrid = algorithm.endswith("hybrid")
+    par = np.ones(2) if reg_par is None else np.asarray(reg_par, dtype=np.float64).reshape(-1)
+    if par.size < (2 if hybrid else 1):
+        raise ValueError(f"recon: algorithm={algorithm!r} needs reg_par = " + ("[beta, delta]" if hybrid else "[beta]") +
+                         f" (got {reg_par!r})")
+    beta, delta = float(par[0]), float(par[1]) if hybrid else 1.0
+    if not (np.isfinite(beta) and beta >= 0):
+        raise ValueError(f"recon: reg_par[0] (beta, the penalty's weight) must be finite and not negative (got {beta})")
+    if not (np.isfinite(delta) and delta > 0):
+        raise ValueError(f"recon: reg_par[1] (delta, the hybrid penalty's edge scale) must be positive (got {delta})")
+    return beta, delta, hybrid
+
+
+def _pml(data, tables, gx, gy, num_iter, init, blocks, beta, delta, hybrid):
+    """libtomo pml_quad.c / pml_hybrid.c / ospml_*.c: _mlem's plan and forward launch; the back-projector's store is the penalized
+    update (ctpvae_siddon_bwd_sel_pml_f32), which reads the neighbours of every pixel from the iterate the launch started with: x
+    ping-pongs between two buffers, swapped after every block."""
+    lib = _lib.load()
+    sin_t, cos_t, quad = tables
+    oy, dt, dx = data.shape
+    dev = data.device
+    center, sp = ctypes.c_float(dx / 2.0), _stream_ptr()
+    geo = (gx, gy, sin_t.data_ptr(), cos_t.data_ptr(), quad.data_ptr(), dt, dx, center)
+    ws = _bp_workspace(tables, oy, gx, gy, dt, dx, dev)
+    need = lib.ctpvae_siddon_fwd_workspace_bytes(oy, gx, gy)
+    _lib.check(need, "siddon_fwd_workspace_bytes")
+    fws = torch.empty(int(need), dtype=torch.uint8, device=dev) if need else None
+    ones = torch.ones((1, dt, dx), dtype=torch.float32, device=dev)
+    plan = []
+    for b in blocks:
+        sel = None if b is None else torch.from_numpy(b).to(dev)
+        n = dt if b is None else int(b.size)
+        colsum = _fwd._new_output((1, gx, gy), torch.float32, dev)                        # sum_dist of the block
+        _lib.check(lib.ctpvae_siddon_bwd_sel_scaled_f32(ones.data_ptr(), 1, *geo, sel.data_ptr() if sel is not None else None, n,
+                                                        ws.data_ptr(), None, 0, colsum.data_ptr(), sp), "siddon_bwd_sel_scaled")
+        plan.append((sel, n, colsum))
+    x, x2 = init.contiguous().clone(), _fwd._new_output(init.shape, torch.float32, dev)
+    ratio = _fwd._new_output((oy * max(n for _, n, _ in plan) * dx,), torch.float32, dev)   # a block uses its first oy * n * dx
+    for _ in range(int(num_iter)):
+        for sel, n, colsum in plan:
+            selp = sel.data_ptr() if sel is not None else None
+            _lib.check(lib.ctpvae_siddon_fwd_ratio_f32(x.data_ptr(), oy, *geo, selp, n, data.data_ptr(),
+                                                       fws.data_ptr() if fws is not None else None, ratio.data_ptr(), sp),
+                       "siddon_fwd_ratio")
+            _lib.check(lib.ctpvae_siddon_bwd_sel_pml_f32(ratio.data_ptr(), oy, *geo, selp, n, ws.data_ptr(), colsum.data_ptr(),
+                                                         ctypes.c_float(beta), ctypes.c_float(delta), int(hybrid), x.data_ptr(),
+                                                         x2.data_ptr(), sp), "siddon_bwd_sel_pml")
+            x, x2 = x2, x
+    return x
+
+
 _TV_WARNED = False
 
 
@@ -274,12 +348,16 @@ def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_r
           num_iter=1, filter_name=None, filter_par=None, reg_par=None, num_block=None, ind_block=None, **kwargs):
     """tomopy.recon's call shape for the algorithms above.  tomo: [angles][slices][dx] (sinogram_order=False) or
     [slices][angles][dx] (True), a float tensor on a HIP device.  Returns [slices][num_gridx][num_gridy] float32.
-    filter_name None = tomopy's default for the algorithm ('parzen' for gridrec, 'none' for fbp).  num_block / ind_block: osem's
-    ordered subsets (tomopy's defaults 1 / arange(angles)); given with another algorithm they are refused."""
+    filter_name None = tomopy's default for the algorithm ('parzen' for gridrec, 'none' for fbp).  num_block / ind_block: the
+    ordered subsets of osem, ospml_quad and ospml_hybrid (tomopy's defaults 1 / arange(angles)); given with another algorithm they
+    are refused.  reg_par: tv's weight; [beta] of pml_quad / ospml_quad, [beta, delta] of the hybrid ones (None: tomopy's ones)."""
     if algorithm not in ALGORITHMS:
         raise ValueError(f"recon: unknown algorithm {algorithm!r}; available: {ALGORITHMS}")
-    if algorithm != "osem" and (num_block is not None or ind_block is not None):
-        raise ValueError(f"recon: num_block / ind_block belong to algorithm='osem' (got algorithm={algorithm!r})")
+    if algorithm not in _BLOCKED and (num_block is not None or ind_block is not None):
+        raise ValueError(f"recon: num_block / ind_block belong to algorithm='osem' and to 'ospml_quad' / 'ospml_hybrid' "
+                         f"(got algorithm={algorithm!r})")
+    if algorithm in _PML:
+        beta, delta, hybrid = _pml_reg_par(algorithm, reg_par)
     if filter_name is None:
         filter_name = _DEFAULT_FILTER.get(algorithm, "none")
     data = _as_device_f32(tomo, "tomo")
@@ -293,7 +371,9 @@ def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_r
     if center is not None and float(center) != dx / 2.0:
         raise NotImplementedError("recon: only center=None (the detector's middle, as every reference call passes) is built")
     gx, gy = int(num_gridx or dx), int(num_gridy or dx)
-    blocks = _osem_blocks(dt, num_block, ind_block) if algorithm == "osem" else [None]
+    if algorithm in _PML and (gx < 2 or gy < 2):
+        raise ValueError(f"recon: algorithm={algorithm!r} needs a grid of at least 2 x 2 for its neighbourhood penalty (got {gx} x {gy})")
+    blocks = _osem_blocks(dt, num_block, ind_block) if algorithm in _BLOCKED else [None]
     if oy == 0:
         return data.new_empty((0, gx, gy))
     with torch.cuda.device(data.device):
@@ -320,6 +400,8 @@ def recon(tomo, theta, center=None, sinogram_order=False, algorithm=None, init_r
             return _tv(data, tables, gx, gy, num_iter, init, lam)
         if algorithm in ("mlem", "osem"):
             return _mlem(data, tables, gx, gy, num_iter, init, blocks)
+        if algorithm in _PML:
+            return _pml(data, tables, gx, gy, num_iter, init, blocks, beta, delta, hybrid)
         return _sirt(data, tables, gx, gy, num_iter, init)
 
 

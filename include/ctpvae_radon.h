@@ -39,6 +39,8 @@
  *   ctpvae_siddon_bwd_f32 / _rownorm_f32       tomopy.recon(algorithm='fbp' | 'sirt') behind iradon_all / evaluate_sinogram
  *                                              ctvae/helper_functions.py:445-457,503,514
  *   ctpvae_siddon_fwd_ratio_f32 / _bwd_sel_mul_f32   tomopy.recon(algorithm='mlem' | 'osem') behind the same two callers
+ *   ctpvae_siddon_bwd_sel_pml_f32              tomopy.recon(algorithm='pml_quad' | 'pml_hybrid' | 'ospml_quad' | 'ospml_hybrid'), with
+ *                                              _fwd_ratio as its forward
  *   ctpvae_gridrec_*                           tomopy.recon(algorithm='gridrec'), the default of iradon_all / evaluate_sinogram
  *                                              ctvae/helper_functions.py:445-457,503; ctvae/main_ct_vae.py:111-112
  *   ctpvae_fbp_filter_f64 / _backproject{,_bwd}_f64   iradon  ctvae/fbp_tensorflow.py:14-75
@@ -474,6 +476,38 @@ int ctpvae_siddon_fwd_ratio_f32(const float *obj_dev, int oy, int ox, int oz, co
 int ctpvae_siddon_bwd_sel_mul_f32(const float *ratio_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                                   const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
                                   const void *workspace_dev, const float *colsum_dev, float *x_dev, ctpvae_stream_t stream);
+/* Penalized likelihood (tomopy.recon(algorithm='pml_quad' | 'pml_hybrid' | 'ospml_quad' | 'ospml_hybrid'); libtomo pml_quad.c /
+ * pml_hybrid.c / ospml_quad.c / ospml_hybrid.c restated [3P-recalled: TomoPy 1.11.0], the recollection checked by re-deriving the
+ * update as De Pierro's separable surrogate): per block and iteration _fwd_ratio above, then this call -- again TWO launches with
+ * nothing elementwise in between (ct_pvae_amd/recon.py _pml).  _bwd_sel_mul's gather, operands and workspace; its store is, per
+ * pixel c = i * oz + j of every slice, in float32 and in this order, with u = (A_sel^T ratio)[c] and x = x_in[c]:
+ *     E     = -(x * u)
+ *     F = 0 ; P = 0 ; for q in the neighbour order below, skipping neighbours outside the grid:
+ *             r   = x - x_in[k_q]
+ *             gam = 1                                    (hybrid == 0: quadratic penalty)
+ *                 = 1 / (1 + fabs(r / delta))            (hybrid != 0)
+ *             t   = ((2 * beta) * w_q) * gam             (quadratic: (2 * beta) * w_q)
+ *             F  += t ;  P -= t * (x + x_in[k_q])
+ *     G     = P + colsum[c]
+ *     S     = sqrtf(G * G - (8 * E) * F)
+ *     x_out[c] = (-2 * E) / (G + S)        where G > 0
+ *              = (-G + S) / (4 * F)        where G <= 0 and F != 0        (libtomo's form, which libtomo uses everywhere)
+ *              = x                         where G <= 0 and F == 0        (only with beta == 0: a pixel no ray of the block crosses)
+ *   Neighbour order (di, dj): (0,+1) (0,-1) (+1,0) (-1,0) (+1,+1) (+1,-1) (-1,+1) (-1,-1) -- libtomo's ind0 + 1, - 1, + ngridy,
+ *   - ngridy, + ngridy + 1, + ngridy - 1, - ngridy + 1, - ngridy - 1.  Weights: direct a, diagonal a / sqrt(2), a = 1 / (n_direct +
+ *   n_diag / sqrt(2)) over the neighbours that exist, libtomo's tables as float32 literals: interior 0.1464466094 / 0.1035533906,
+ *   edge 0.2265409197 / 0.1601886205, corner 0.3693980625 / 0.2612038750.  Every neighbour is read from x_in_dev (Jacobi), so
+ *   x_in_dev and x_out_dev [oy][ox][oz] are distinct buffers the caller swaps; x_in_dev is not written.  colsum_dev [ox][oz]: the
+ *   block's sum_dist.  delta is read only with hybrid != 0.
+ * THE SECOND FLAGGED DEVIATION (beside _fwd_ratio's guarded ratio): where G > 0 the positive root of 2 F x^2 + G x + E = 0 is taken
+ * in its cancellation-free form; libtomo's form subtracts two nearly equal numbers there (beta = 0.01, 20 float32 iterations against
+ * the same iteration in float64: 2.6e-4 to 5.7e-4 of the image's maximum, against 8.7e-7 for this form; tests/test_pml_cpu.py).
+ * EINVAL before any HIP call: a null pointer, x_in_dev == x_out_dev, ox < 2 or oz < 2, beta negative or not finite, hybrid with
+ * delta not > 0.  oy == 0 returns without a launch; long batches go in chunks. */
+int ctpvae_siddon_bwd_sel_pml_f32(const float *ratio_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
+                                  const int *quad_dev, int dt_all, int dx, float center, const int *sel_dev, int n_sel,
+                                  const void *workspace_dev, const float *colsum_dev, float beta, float delta, int hybrid,
+                                  const float *x_in_dev, float *x_out_dev, ctpvae_stream_t stream);
 /* Round 4: an iteration of the TV STAND-IN of tomopy.recon(algorithm='tv') (README.md:221 of the reference asks for 'tv';
  * libtomo's tv.c is NOT restated -- ct_pvae_amd/recon.py says so on every call) as TWO projector launches instead of ~15 torch
  * ops around them: the diagonally preconditioned Chambolle-Pock iteration for min 1/2 |A x - b|^2 + lam TV(x) on K = (A; grad),
