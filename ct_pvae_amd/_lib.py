@@ -147,6 +147,11 @@ SIGNATURES = {
     "ctpvae_poisson_measure_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_ulonglong, _vp, _vp]),
     "ctpvae_philox4x32_10": (_c_int, [_vp, _vp, _vp]),
     "ctpvae_loglik_bwd_f32": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _vp, _c_float, _vp, _vp, _vp]),
+    "ctpvae_hmc_state_floats": (_c_int, [_c_int]),
+    "ctpvae_hmc_init_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp, _vp, _vp,
+                                     _c_float, _vp]),
+    "ctpvae_hmc_run_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp,
+                                    _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

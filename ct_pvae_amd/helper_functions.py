@@ -15,7 +15,7 @@ from . import forward_functions as _fwd  # noqa: E402  (NaN-poisoned outputs in 
 from . import _lib, forward_functions
 from .forward_functions import _cached_plan, _current_device, _stream_ptr, as_angle_index, project_tf_fast
 
-__all__ = ["create_sinogram", "create_sinograms", "calculate_log_prob_M_given_R", "gaussian_poisson_log_prob", "poisson_log_prob"]
+__all__ = ["create_sinogram", "create_sinograms", "calculate_log_prob_M_given_R", "gaussian_poisson_log_prob", "poisson_log_prob", "toy_dist"]
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -676,3 +676,11 @@ def _two_step_log_prob(output_sample, mask, proj_sample, poisson_noise_multiplie
     if reduce == "per_object":
         return _ObjectSums.apply(logp.unsqueeze(-1), partition)
     return logp.unsqueeze(-1)
+
+
+def toy_dist(mix_prob=0.3,
+             conc_0=(0.35580334, 0.94963009, 0.60227688, 0.43061459),
+             conc_1=(0.00390356, 0.44335424, 0.83152378, 0.52733124)):
+    """The prior of the 2 x 2 toy problem (ctvae/helper_functions.py:531-559: a two-component mixture of Dirichlets) as plain
+    numbers, (weights [2], concentrations [2][4]) in float32 -- what mcmc.hmc_sample takes as `prior`."""
+    return (np.array([mix_prob, 1.0 - mix_prob], np.float32), np.array([conc_0, conc_1], np.float32))

@@ -631,6 +631,42 @@ int ctpvae_poisson_measure_f32(const float *sino_dev, const float *mask_dev, int
 /* Host-side known-answer hook for the generator: the four words of Philox4x32-10(counter4, key2) (host pointers). */
 int ctpvae_philox4x32_10(const unsigned *counter4, const unsigned *key2, unsigned *out4);
 
+/* ---- HMC posterior sampler for small objects (bin/toy_mcmc_v2.py, ctvae/toy_mcmc_v2_functions.py:66-95): one 64-lane wave per chain,
+ * n_steps whole transitions per launch (csrc/hmc.hip states the target density, the orders of its sums and the layout of the random
+ * numbers).  Square objects of K = N * N <= 64 pixels, the rotate model with NEAREST sampling on the unpadded canvas (P = N), at most
+ * CTPVAE_HMC_MAX_ANGLES angles, fp32.  T8_dev / Tinv8_dev [A][8]: the tables of ctpvae_rotate_transforms(_host)_f32 for H = W = N.
+ * C chains; chain c samples the posterior of object c / chains_per_object: mask_dev [B][A], meas_dev [B][A][N], B = C /
+ * chains_per_object.  The prior is a mixture of M <= CTPVAE_HMC_MAX_COMPONENTS Dirichlets: logw_dev [M] (log weights), alpha_dev
+ * [M][K] (concentrations), lbeta_dev [M] (log of the multivariate beta function of each row), all fp32 on the device, computed by
+ * the caller (in float64, rounded once).
+ *   _state_floats(K): floats of one chain's carried state -- x [K-1], dT/dx [K-1], T, the step size, and the BITS of the unsigned
+ *     32-bit index of the chain's next step: 2K + 1.
+ *   _init_f32: state_dev [C][2K + 1] from simplex starting points start_dev [C][K] (the inverse bijector; every entry > 0), or from
+ *     x = 0 when start_dev is NULL; evaluates T and dT/dx there; step index 0.
+ *   _run_f32: n_steps (1 .. CTPVAE_HMC_MAX_STEPS) transitions of every chain from its state's step index t0, with L
+ *     (1 .. CTPVAE_HMC_MAX_LEAPFROGS) leapfrog steps each; the step size adapts (x 1.01f if min(log accept ratio, 0) > log 0.75, else
+ *     / 1.01f, a NaN ratio included) while the step's index < num_adaptation_steps.  The draws of chain c at step t depend on (seed,
+ *     first_chain + c, t) alone, so a run may be cut into launches, and its chains into calls, in any way.  Steps with index >=
+ *     n_keep_from are stored: the first such step of THIS launch is row 0 of samples_out_dev [rows][C][K] (points of the simplex),
+ *     lar_out_dev, accepted_out_dev (0.0f / 1.0f), target_out_dev [rows][C] (log accept ratio, decision, T after the decision);
+ *     rows <= n_steps.  CTPVAE_HMC_MAX_STEPS bounds the time of one launch: the largest power of two that keeps a launch of
+ *     the slowest shape measured with 5 leapfrog steps (8 x 8, 180 angles: 149 us per transition) under 100 ms on the MI355X.  At
+ *     the extremes this entry point admits (256 angles, 32 leapfrog steps) a full launch takes about 644 ms
+ *     (profiles/hmc_timing.txt). */
+#define CTPVAE_HMC_MAX_ANGLES 256
+#define CTPVAE_HMC_MAX_COMPONENTS 4
+#define CTPVAE_HMC_MAX_LEAPFROGS 32
+#define CTPVAE_HMC_MAX_STEPS 512
+int ctpvae_hmc_state_floats(int K);
+int ctpvae_hmc_init_f32(float *state_dev, int C, int chains_per_object, int N, const float *T8_dev, const float *Tinv8_dev, int A,
+                        const float *mask_dev, const float *meas_dev, float pnm, int M, const float *logw_dev, const float *alpha_dev,
+                        const float *lbeta_dev, const float *start_dev, float step_size, ctpvae_stream_t stream);
+int ctpvae_hmc_run_f32(float *state_dev, int C, unsigned first_chain, int chains_per_object, int N, const float *T8_dev,
+                       const float *Tinv8_dev, int A, const float *mask_dev, const float *meas_dev, float pnm, int M,
+                       const float *logw_dev, const float *alpha_dev, const float *lbeta_dev, int L, int n_steps, unsigned n_keep_from,
+                       unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev, float *lar_out_dev,
+                       float *accepted_out_dev, float *target_out_dev, ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
