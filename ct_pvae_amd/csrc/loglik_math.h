@@ -63,8 +63,10 @@ __device__ __forceinline__ float gaussian_poisson_logp(float proj, float m, floa
 
 // d logp / d proj (the mask factor included) and d logp / d pnm of the same sample: what the backward multiplies the
 // upstream gradient by.  One expression for loglik_bwd_kernel and for the projector epilogue that stores dlp.  Nothing pins
-// its bits (the tests hold it to float64 autograd at 1e-4), so its quotients are products with TWO reciprocals, 1 / scale (the log-probability's refined one) and
-// 1 / root (v_rcp_f32), and with the caller's 1 / pnm (once per kernel) -- written with a division per quotient (round 2) the derivative
+// its bits -- the tests hold EVERY sample of it, and of d / d pnm, to the float64 formula within a per-sample float32 error bar (tests/np_twin_gauss.py:
+// |got - ref| <= 4 R bar, R the numpy twin's own excess; tests/test_gpu_gauss_loglik.py) --, so its quotients are products with TWO reciprocals,
+// 1 / scale (the log-probability's refined one) and 1 / root (v_rcp_f32), and with the caller's 1 / pnm (once per kernel) -- written with a division
+// per quotient (round 2) the derivative
 // was six divisions and a second root, ~110 of the ~180 vector instructions a sample cost.  (Measured on one box: config 5's
 // forward + likelihood + sums 122.4 -> 122.2 us, the training call 9.9 -> 9.85 us -- the epilogues' arithmetic hides under
 // their memory traffic; kept because it is less code, not because it is faster.)
