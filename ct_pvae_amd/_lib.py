@@ -152,6 +152,11 @@ SIGNATURES = {
                                      _c_float, _vp]),
     "ctpvae_hmc_run_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp,
                                     _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_tn_head_fwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,
+                                        _vp]),
+    "ctpvae_tn_head_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "ctpvae_tn_head_uniforms_host_f32": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp]),
 }
 
 _lib = None

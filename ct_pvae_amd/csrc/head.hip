@@ -1,0 +1,298 @@
+// head.hip -- the P-VAE decoder's TruncatedNormal output head (ctvae/helper_functions.py:198-201, :273; ct_pvae_amd/trainer.py
+// positive_range / TruncatedNormal.rsample / .log_prob) as ONE forward and ONE backward launch: the reparameterised sample of every
+// pixel, its log-density and the per-object sum of the log-densities; the backward gives what autograd gives on that composition.
+//
+// The function, per pixel, fp32 (EPS = FLT_EPSILON, LO = 1e-7f, HI = (float)(1 - 1e-7) = 1 - 2^-23; low = 0, high = 1e10 of the
+// truncation are fixed: Phi((1e10 - loc) / scale) is exactly 1):
+//   pr(t)  = t >= 1 ? t : exp(t - 1) + EPS;   loc = pr(alpha), scale = pr(beta)
+//   a      = -loc / scale;   Pa = Phi(a);   Z = max(1 - Pa, 1e-30)           (loc > 0: Z >= 0.5, the clamp never acts)
+//   p      = clamp(Pa + u Z, LO, HI);   z = ndtri(p);   x = max(loc + scale z, 0)
+//   zeta   = (x - loc) / scale;   lp = ((-zeta^2 / 2 - log(2 pi) / 2) - log scale) - log Z
+// How it is evaluated: Pa = erfc(-a / sqrt 2) / 2 and Z = erfc(a / sqrt 2) / 2 each from its own erfc (both keep their relative
+// accuracy: 0.5 (1 + erf) loses Pa below 1e-7), and on the upper half (Pa + u Z > 0.5) the quantile is taken from the complement,
+//   1 - (Pa + u Z) = Z (1 - u),   z = -ndtri(max(Z (1 - u), 1 - HI))
+// -- ndtri amplifies the rounding of its argument by sqrt(2 pi) e^(z^2 / 2) (1.8e6 at the clamp), and next to 1 that rounding is
+// 2^-24 absolute whereas the complement's is 2^-24 RELATIVE.  The clamp of p at HI is the clamp of the complement at 1 - HI = 2^-23.
+//
+// The backward, for the cotangents g_x (per pixel) and G = g_LP[object] (torch's conventions: clamp passes where lo <= v <= hi,
+// erf'(t) = 2 / sqrt(pi) e^(-t^2), ndtri'(p) = sqrt(2 pi) e^(z^2 / 2)):
+//   gx0    = [loc + scale z >= 0] (g_x - G zeta / scale)                       (lp's own path through x included)
+//   gp     = [LO <= Pa + u Z <= HI] gx0 scale sqrt(2 pi) e^(z^2 / 2)
+//   ga     = phi(a) (gp (1 - u) + G / Z),   phi(a) = e^(-a^2 / 2) / sqrt(2 pi)  (p = Pa + u (1 - Pa); -log Z)
+//   gloc   = (gx0 + G zeta / scale) - ga / scale
+//   gscale = (gx0 z + G (zeta^2 - 1) / scale) - ga a / scale
+//   g_alpha = gloc pr'(alpha),  g_beta = gscale pr'(beta),   pr'(t) = t >= 1 ? 1 : exp(t - 1)
+// Nothing is saved for it: it re-evaluates the pixel from alpha, beta and the regenerated u with the forward's own code (the same
+// fp32 operations, so the same clamp decisions).
+//
+// Random numbers: Philox4x32-10 (philox.h).  Pixel `pixel` of object o has the 64-bit flat index e = (first_object + o) * pix + pixel
+// and takes word e & 3 of the block  philox4x32_10(lo32(e >> 2), hi32(e >> 2), draw, kHeadTag, seed lo, seed hi);
+// u = ((w >> 8) + 0.5f) * 2^-24 in fp32 (hmc.hip's form): never 0, never 1.  u depends on (seed, draw, e) alone, so a batch cut
+// into calls (or ranks) with first_object draws what the whole batch draws.  A non-null u_in [n][pix] replaces the generator.
+//
+// Layout and the order of the per-object sum (fixed by the pixel's index INSIDE its object, so LP[o] has the same bits whatever n,
+// first_object and the object's alignment in memory are).  One workgroup of 1024 threads = 16 waves per object; no atomics.
+//   quad q of the object = its pixels 4q .. 4q+3:  s_q = ((lp_4q + lp_4q+1) + lp_4q+2) + lp_4q+3       (pixels past pix add +0.0f)
+//   thread t takes the quads t, t + 1024, t + 2048, ...:  acc_t = ((0 + s_t) + s_(t+1024)) + ...      (a thread without a quad: +0.0f)
+//   wave w = threads 64w .. 64w+63:  W_w = wave_sum(acc) -- the xor butterfly 32, 16, 8, 4, 2, 1 of loglik_math.h
+//   LP[o] = ((W_0 + W_1) + W_2) + ... + W_15                                                          (ascending, one at a time)
+// The longest chain of additions is 3 + ceil(ceil(pix / 4) / 1024) + 6 + 15.
+// A quad is moved with one 16-byte access when it is whole and 16-byte aligned in memory (object offset o * pix a multiple of 4,
+// pointers 16-byte aligned), with guarded 4-byte accesses otherwise.  The backward has no sum: it walks the n * pix pixels as
+// memory quads, 256 threads per workgroup.
+#include <climits>
+#include <initializer_list>
+
+#include "common.h"
+#include "loglik_math.h"
+#include "philox.h"
+
+namespace ctpvae {
+
+constexpr unsigned kHeadTag = 0x544E48u;     // "TNH": the fourth counter word (hmc.hip: 0x484D43, poisson.hip: 0)
+constexpr int kHeadFwdThreads = 1024;
+constexpr int kHeadBwdThreads = 256;
+constexpr float kHeadEps = 1.1920928955078125e-07f;    // FLT_EPSILON, positive_range's offset
+constexpr float kHeadPLo = 1e-7f;
+constexpr float kHeadQLo = 1.1920928955078125e-07f;    // 1 - HI, HI = (float)(1 - 1e-7) = 1 - 2^-23
+constexpr float kInvSqrt2 = 0.70710678118654752440f;
+constexpr float kSqrt2Pi = 2.50662827463100050242f;
+constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
+
+__host__ __device__ inline float head_u24(unsigned w) { return ((float)(w >> 8) + 0.5f) * 5.9604644775390625e-08f; }
+
+__host__ __device__ inline Philox4 head_block(unsigned long long blk, unsigned draw, unsigned k0, unsigned k1)
+{
+    return philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), draw, kHeadTag, k0, k1);
+}
+// word k (0 .. 3) of a block, without indexing the array by a run-time value
+__host__ __device__ inline unsigned head_word(const Philox4 &b, unsigned k)
+{
+    return k == 0 ? b.w[0] : (k == 1 ? b.w[1] : (k == 2 ? b.w[2] : b.w[3]));
+}
+// the uniforms of the four pixels e .. e+3 (one block when e is a multiple of 4, two otherwise)
+__device__ __forceinline__ void head_uniforms4(unsigned long long e, unsigned draw, unsigned k0, unsigned k1, float (&u)[4])
+{
+    const unsigned s = (unsigned)e & 3u;
+    const Philox4 A = head_block(e >> 2, draw, k0, k1);
+    Philox4 B = A;
+    if (s != 0) B = head_block((e >> 2) + 1, draw, k0, k1);
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) u[j] = head_u24(s + j < 4 ? head_word(A, s + j) : head_word(B, s + j - 4));
+}
+
+struct TnPixel {
+    float scale, dloc, dscale;   // pr(beta), pr'(alpha), pr'(beta)
+    float a, Z, omu, z, D;       // D = ndtri'(p) (backward only)
+    float x, zeta, lp;
+    bool pass_p, pass_x;         // the clamps of p and of x let the gradient through
+};
+
+template <bool BWD>
+__device__ __forceinline__ TnPixel tn_pixel(float alpha, float beta, float u)
+{
+    TnPixel r;
+    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
+    const float loc = alpha >= 1.0f ? alpha : ea + kHeadEps;
+    r.scale = beta >= 1.0f ? beta : eb + kHeadEps;
+    r.dloc = alpha >= 1.0f ? 1.0f : ea;
+    r.dscale = beta >= 1.0f ? 1.0f : eb;
+    r.a = -loc / r.scale;
+    const float t = r.a * kInvSqrt2;
+    const float Pa = 0.5f * erfcf(-t);
+    r.Z = fmaxf(0.5f * erfcf(t), 1e-30f);
+    r.omu = 1.0f - u;
+    const float p0 = Pa + u * r.Z, q0 = r.Z * r.omu;
+    const bool upper = p0 > 0.5f;
+    r.pass_p = upper ? q0 >= kHeadQLo : p0 >= kHeadPLo;
+    const float zt = normcdfinvf(upper ? fmaxf(q0, kHeadQLo) : fmaxf(p0, kHeadPLo));
+    r.z = upper ? -zt : zt;
+    const float x0 = loc + r.scale * r.z;
+    r.pass_x = x0 >= 0.0f;
+    r.x = fmaxf(x0, 0.0f);
+    r.zeta = (r.x - loc) / r.scale;
+    r.lp = ((-0.5f * (r.zeta * r.zeta) - kHalfLog2Pi) - logf(r.scale)) - logf(r.Z);
+    if constexpr (BWD) r.D = kSqrt2Pi * expf(0.5f * (r.z * r.z));
+    return r;
+}
+
+struct HeadRng {
+    unsigned long long first_pixel;   // first_object * pix
+    unsigned draw, k0, k1;
+    const float *u_in;                // [n][pix] or nullptr
+};
+
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void st4(float *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+// the pixels i .. i+cnt-1 of an array; the rest of the quad reads `fill`
+__device__ __forceinline__ void head_load(const float *p, size_t i, int cnt, bool vec, float fill, float (&v)[4])
+{
+    if (vec && cnt == 4) {
+        const float4 q = ld4(p + i);
+        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[i + j] : fill;
+    }
+}
+__device__ __forceinline__ void head_store(float *p, size_t i, int cnt, bool vec, const float (&v)[4])
+{
+    if (vec && cnt == 4) {
+        st4(p + i, v);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < cnt) p[i + j] = v[j];
+    }
+}
+
+__global__ __launch_bounds__(kHeadFwdThreads) void tn_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+                                                                      int pix, HeadRng rng, int ptr_aligned, float *__restrict__ x_out,
+                                                                      float *__restrict__ lp_sum, float *__restrict__ lp_elem)
+{
+    __shared__ float wsum[kHeadFwdThreads / 64];
+    const int o = blockIdx.x, t = threadIdx.x;
+    const size_t base = (size_t)o * pix;
+    const bool vec = ptr_aligned != 0 && (base & 3) == 0;
+    const int quads = (pix + 3) >> 2;
+    float acc = 0.0f;
+    for (int q = t; q < quads; q += kHeadFwdThreads) {
+        const int r = 4 * q;
+        const int cnt = pix - r < 4 ? pix - r : 4;
+        const size_t i = base + r;
+        float al[4], be[4], u[4], x[4], lp[4];
+        head_load(alpha, i, cnt, vec, 1.0f, al);
+        head_load(beta, i, cnt, vec, 1.0f, be);
+        if (rng.u_in != nullptr) head_load(rng.u_in, i, cnt, vec, 0.5f, u);
+        else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const TnPixel px = tn_pixel<false>(al[j], be[j], u[j]);
+            x[j] = px.x;
+            lp[j] = j < cnt ? px.lp : 0.0f;
+        }
+        head_store(x_out, i, cnt, vec, x);
+        if (lp_elem != nullptr) head_store(lp_elem, i, cnt, vec, lp);
+        acc += ((lp[0] + lp[1]) + lp[2]) + lp[3];
+    }
+    const float w = wave_sum(acc);
+    if ((t & 63) == 0) wsum[t >> 6] = w;
+    __syncthreads();
+    if (t == 0) {
+        float s = wsum[0];
+#pragma unroll
+        for (int k = 1; k < kHeadFwdThreads / 64; ++k) s += wsum[k];
+        lp_sum[o] = s;
+    }
+}
+
+__global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+                                                                      long long total, int pix, HeadRng rng, int ptr_aligned,
+                                                                      const float *__restrict__ g_x, const float *__restrict__ g_lp,
+                                                                      float *__restrict__ g_alpha, float *__restrict__ g_beta)
+{
+    const long long i0 = 4 * ((long long)blockIdx.x * kHeadBwdThreads + threadIdx.x);
+    if (i0 >= total) return;
+    const int cnt = total - i0 < 4 ? (int)(total - i0) : 4;
+    const size_t i = (size_t)i0;
+    const bool vec = ptr_aligned != 0;
+    float al[4], be[4], u[4], gx[4], ga[4], gb[4];
+    head_load(alpha, i, cnt, vec, 1.0f, al);
+    head_load(beta, i, cnt, vec, 1.0f, be);
+    if (rng.u_in != nullptr) head_load(rng.u_in, i, cnt, vec, 0.5f, u);
+    else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
+    if (g_x != nullptr) head_load(g_x, i, cnt, vec, 0.0f, gx);
+    else gx[0] = gx[1] = gx[2] = gx[3] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // the pixel's object: total < 2^31, so 32-bit division (pixels past the end read object n - 1)
+        const unsigned e = (unsigned)(j < cnt ? i0 + j : i0);
+        const float G = g_lp != nullptr ? g_lp[e / (unsigned)pix] : 0.0f;
+        const TnPixel px = tn_pixel<true>(al[j], be[j], u[j]);
+        const float rs = 1.0f / px.scale;
+        const float gzs = G * px.zeta * rs;
+        const float gx0 = px.pass_x ? gx[j] - gzs : 0.0f;
+        const float gp = px.pass_p ? gx0 * px.scale * px.D : 0.0f;
+        const float phi = kInvSqrt2Pi * expf(-0.5f * (px.a * px.a));
+        const float gA = phi * (gp * px.omu + G / px.Z);
+        const float gloc = (gx0 + gzs) - gA * rs;
+        const float gscale = (gx0 * px.z + G * (px.zeta * px.zeta - 1.0f) * rs) - gA * px.a * rs;
+        ga[j] = gloc * px.dloc;
+        gb[j] = gscale * px.dscale;
+    }
+    head_store(g_alpha, i, cnt, vec, ga);
+    head_store(g_beta, i, cnt, vec, gb);
+}
+
+static int head_check(const char *what, const void *alpha, const void *beta, int n, int pix, long long first_object)
+{
+    CTPVAE_REQUIRE(alpha && beta, "%s: null pointer", what);
+    CTPVAE_REQUIRE(n > 0 && pix > 0, "%s: sizes must be positive (n=%d pix=%d)", what, n, pix);
+    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "%s: n * pix must fit 31 bits (n=%d pix=%d)", what, n, pix);
+    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
+                   "%s: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", what, first_object);
+    return CTPVAE_OK;
+}
+
+static bool head_aligned16(std::initializer_list<const void *> ptrs)
+{
+    for (const void *p : ptrs)
+        if (((size_t)p & 15) != 0) return false;   // (a null pointer counts as aligned)
+    return true;
+}
+
+}  // namespace ctpvae
+
+using namespace ctpvae;
+
+extern "C" {
+
+int ctpvae_tn_head_fwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                           unsigned long long seed, unsigned draw, const float *u_dev, float *x_out_dev, float *lp_sum_out_dev,
+                           float *lp_elem_out_dev, ctpvae_stream_t stream)
+{
+    if (int rc = head_check("tn_head_fwd", alpha_dev, beta_dev, n, pix, first_object)) return rc;
+    CTPVAE_REQUIRE(x_out_dev && lp_sum_out_dev, "tn_head_fwd: null output pointer");
+    const HeadRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32), u_dev};
+    const int aligned = head_aligned16({alpha_dev, beta_dev, u_dev, x_out_dev, lp_elem_out_dev}) ? 1 : 0;
+    hipLaunchKernelGGL(tn_head_fwd_kernel, dim3(n), dim3(kHeadFwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, pix, rng, aligned,
+                       x_out_dev, lp_sum_out_dev, lp_elem_out_dev);
+    CTPVAE_LAUNCH_CHECK("tn_head_fwd_kernel");
+    return CTPVAE_OK;
+}
+
+int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                           unsigned long long seed, unsigned draw, const float *u_dev, const float *g_x_dev, const float *g_lp_dev,
+                           float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream)
+{
+    if (int rc = head_check("tn_head_bwd", alpha_dev, beta_dev, n, pix, first_object)) return rc;
+    CTPVAE_REQUIRE(g_alpha_out_dev && g_beta_out_dev, "tn_head_bwd: null output pointer");
+    const HeadRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32), u_dev};
+    const int aligned = head_aligned16({alpha_dev, beta_dev, u_dev, g_x_dev, g_alpha_out_dev, g_beta_out_dev}) ? 1 : 0;
+    const long long total = (long long)n * pix;
+    const long long per_block = 4ll * kHeadBwdThreads;
+    const unsigned grid = (unsigned)((total + per_block - 1) / per_block);
+    hipLaunchKernelGGL(tn_head_bwd_kernel, dim3(grid), dim3(kHeadBwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, total, pix, rng,
+                       aligned, g_x_dev, g_lp_dev, g_alpha_out_dev, g_beta_out_dev);
+    CTPVAE_LAUNCH_CHECK("tn_head_bwd_kernel");
+    return CTPVAE_OK;
+}
+
+int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host)
+{
+    CTPVAE_REQUIRE(u_out_host, "tn_head_uniforms_host: null pointer");
+    CTPVAE_REQUIRE(n > 0 && pix > 0, "tn_head_uniforms_host: sizes must be positive (n=%d pix=%d)", n, pix);
+    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "tn_head_uniforms_host: n * pix must fit 31 bits (n=%d pix=%d)", n, pix);
+    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
+                   "tn_head_uniforms_host: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", first_object);
+    const unsigned long long e0 = (unsigned long long)first_object * (unsigned long long)pix;
+    const long long total = (long long)n * pix;
+    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+    for (long long i = 0; i < total; ++i) {
+        const unsigned long long e = e0 + (unsigned long long)i;
+        u_out_host[i] = head_u24(head_word(head_block(e >> 2, draw, k0, k1), (unsigned)e & 3u));
+    }
+    return CTPVAE_OK;
+}
+
+}  // extern "C"

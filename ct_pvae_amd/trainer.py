@@ -37,6 +37,7 @@ from .create_masks import create_all_masks
 from .fbp import iradon_all
 from .forward_functions import num_proj_pix
 from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
+from .output_head import truncated_normal_head
 
 EPS32 = float(np.finfo(np.float32).eps)
 
@@ -232,7 +233,12 @@ def kl_normal_std(loc, scale):
 # ---------------------------------------------------------------------------------------------------------
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
-                        use_normal=True, model="rotate", noise="gaussian"):
+                        use_normal=True, model="rotate", noise="gaussian", fused_head=None):
+    """fused_head: None -- the output distribution is the chain of torch operations below, its uniforms from torch's global
+    generator -- or (seed, draw, first_object): sample, log-density and its per-object sum come from ONE launch
+    (output_head.truncated_normal_head, csrc/head.hip), the uniforms from Philox keyed by those three; --normal only."""
+    if fused_head is not None and not use_normal:
+        raise ValueError("fused_head is the TruncatedNormal output head: it needs use_normal=True (the Beta head is not fused)")
     skips = model_encode(input_encode / 300)
     q = None
     if not deterministic:
@@ -257,7 +263,12 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     else:                                                           # reparameterised Beta samples, sample-major
         q_sample = [d.rsample((ns,)).reshape((ns * B,) + tuple(d.concentration1.shape[1:])) for d in q]
     alpha, beta = model_decode(q_sample)
-    if use_normal:
+    if fused_head is not None:
+        seed, draw, first_object = fused_head
+        # (the decoder's alpha / beta are the two channel halves of one tensor: each is made contiguous, one copy)
+        x, head_lp = truncated_normal_head(alpha.contiguous(), beta.contiguous(), seed=seed, draw=draw, first_object=first_object)
+        output_sample = x.permute(0, 3, 1, 2)                            # [ns * B][1][X][Y], a view: the projector gets x itself
+    elif use_normal:
         dist = TruncatedNormal(positive_range(alpha), positive_range(beta), low=0.0, high=1e10)
         output_sample = dist.rsample()                                   # [ns * B][1][X][Y]
         log_prob_R_given_z = dist.log_prob(output_sample)
@@ -272,7 +283,9 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     # :305-306 reduce_sum(..., axis=[0, 1, 2]) of the squeezed [B][A][P] and [B][X][Y] tensors: the log-likelihood of a
     # sample is ONE number for the whole batch (the batch axis is summed too), the KL below is per object; :329-330 then
     # broadcast-subtract, and train_step takes the mean over the batch -- i.e. mean_b(KL_b) - sum_b(loglik_b).
-    log_prob_M = (lp + log_prob_R_given_z.sum(dim=(1, 2, 3))).view(ns, B).sum(dim=1)    # [ns]
+    if fused_head is None:
+        head_lp = log_prob_R_given_z.sum(dim=(1, 2, 3))
+    log_prob_M = (lp + head_lp).view(ns, B).sum(dim=1)                                    # [ns]
     recon = output_sample[(ns - 1) * B:]
     if deterministic:
         kl = lp.new_zeros(B)
@@ -305,6 +318,8 @@ class AngleStream:
 class PVAETrainer:
     def __init__(self, args, device):
         self.args, self.dev = args, device
+        if getattr(args, "fused_head", False) and not args.use_normal:
+            raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
         self.world, self.rank, _ = sharding.env_world()
         self.sqrt_reg = EPS32
         # the nets' shapes are static: --miopen_find lets MIOpen search its convolution algorithms once (14.9 -> 11.5 ms
@@ -312,6 +327,11 @@ class PVAETrainer:
         # and loses)
         if getattr(args, "miopen_find", False):
             torch.backends.cudnn.benchmark = True
+        # --reproducible: MIOpen's default algorithms add the convolutions' weight gradients in an order that changes from run to run
+        # (measured: every conv weight's gradient differs in its last bits between two equal-seed runs, with or without --fused_head;
+        # none does with this switch).  The switch is process-wide, as torch defines it, and changes every convolution's algorithm.
+        if getattr(args, "reproducible", False):
+            torch.backends.cudnn.deterministic = True
         torch.manual_seed(1234 + self.rank)
         a = args
         self.pnm_anneal = math.exp(math.log(a.pnm / a.pnm_start) / max(a.num_iter, 1)) if a.pnm_start else 1.0
@@ -412,11 +432,19 @@ class PVAETrainer:
         """Device side of a step: ELBO, backward, NaN filter + clip, Adam."""
         a = self.args
         pnm_i = self.pnm * pnm_factor
+        # --fused_head: the draw is the global step index (saved and restored with the checkpoint's "iter"), the objects of
+        # this rank follow those of the ranks before it -- a step's samples depend on (--head_seed, step, object) alone.  (The
+        # batch is sample-major, [ns][B]: object (s, b) of rank r is r * ns * B + s * B + b, NOT the s * B_global + r * B + b it
+        # would be in one rank's global batch -- a run is replayable at its own world size, not across world sizes.)
+        fused = None
+        if getattr(a, "fused_head", False):
+            fused = (a.head_seed, self.iter, self.rank * (1 if a.deterministic else a.ns) * input_encode.shape[0])
         loss_vec, kl, loglik, _ = find_loss_vae_unsup(proj_sample, mask, input_encode, self.enc, self.dec, pnm_i,
                                                       self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
                                                       theta=self.theta_host, angles_i=angles_i, pad=self.pad,
                                                       deterministic=a.deterministic, use_normal=a.use_normal,
-                                                      model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"))
+                                                      model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
+                                                      fused_head=fused)
         # ctvae/main_ct_vae.py:478 reduce_mean(loss_M_VAE) / 1e5 = mean_b(KL term) - loglik, where loglik already sums
         # over the batch.  Written so that the ranks' losses ADD UP to the global one (gradients are summed over ranks):
         # each rank contributes its objects' KL / global_B and its own objects' log-likelihood.
@@ -498,7 +526,7 @@ class PVAETrainer:
         self.enc.load_state_dict(ck["enc"])
         self.dec.load_state_dict(ck["dec"])
         self.opt.load_state_dict(ck["opt"])
-        self.kl_anneal, self.iter = ck["kl_anneal"], ck["iter"]
+        self.kl_anneal, self.iter = ck["kl_anneal"], ck["iter"]      # (iter is also --fused_head's draw index)
         with torch.no_grad():
             self.pnm.copy_(ck["pnm"].to(self.dev))
 
@@ -582,6 +610,13 @@ def get_args(argv=None):
     p.add_argument("--noise", choices=["gaussian", "poisson"], default="gaussian",
                    help="noise model of the likelihood term: the reference's Gaussian approximation Normal(loc, sqrt(loc / pnm)), or "
                         "the exact Poisson law the measurements are drawn from (not with --train_pnm)")
+    p.add_argument("--fused_head", action="store_true",
+                   help="sample the TruncatedNormal output and sum its log-density in one launch (csrc/head.hip), with Philox uniforms "
+                        "keyed by (--head_seed, step index, object) instead of torch's global generator; needs --normal")
+    p.add_argument("--reproducible", action="store_true",
+                   help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
+                        "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")
+    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's uniforms")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")
@@ -606,7 +641,10 @@ def get_args(argv=None):
     # synthetic-data knobs (the reference reads these from its dataset folder)
     p.add_argument("--n_pixel", type=int, default=128)
     p.add_argument("--num_angles", type=int, default=180)
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.fused_head and not args.use_normal:
+        raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
+    return args
 
 
 def main(argv=None):

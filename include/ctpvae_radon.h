@@ -667,6 +667,31 @@ int ctpvae_hmc_run_f32(float *state_dev, int C, unsigned first_chain, int chains
                        unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev, float *lar_out_dev,
                        float *accepted_out_dev, float *target_out_dev, ctpvae_stream_t stream);
 
+/* ---- the P-VAE decoder's TruncatedNormal output head (ctvae/helper_functions.py:198-201, :273): sample, log-density and its
+ * per-object sum in ONE launch, their gradients in one more (csrc/head.hip states the function, the order of the sum and the layout
+ * of the random numbers).  alpha_dev, beta_dev [n][pix]: the decoder's raw outputs, pix = X * Y pixels per object, fp32.
+ *   loc = pr(alpha), scale = pr(beta), pr(t) = t >= 1 ? t : exp(t - 1) + FLT_EPSILON;  TruncatedNormal(loc, scale, low 0, high 1e10)
+ *   x = max(loc + scale ndtri(clamp(Pa + u Z, 1e-7, 1 - 1e-7)), 0),  Pa = Phi(-loc / scale), Z = 1 - Pa
+ *   lp = -zeta^2 / 2 - log(2 pi) / 2 - log scale - log Z,  zeta = (x - loc) / scale
+ * u of pixel `pixel` of object o is word e & 3 of Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), draw, 0x544E48), key = seed)
+ * with the flat 64-bit index e = (first_object + o) * pix + pixel, u = ((w >> 8) + 0.5f) * 2^-24: a batch cut into calls with
+ * first_object draws what the whole batch draws.  A non-null u_dev [n][pix] replaces the generator (tests: the clamps cannot be
+ * reached otherwise).
+ *   _fwd_f32: x_out_dev [n][pix], lp_sum_out_dev [n] (the sum of an object's lp in the fixed order of csrc/head.hip: the same bits
+ *     whatever n and first_object), lp_elem_out_dev [n][pix] or NULL.
+ *   _bwd_f32: g_alpha_out_dev, g_beta_out_dev [n][pix] for the cotangents g_x_dev [n][pix] and g_lp_dev [n] (either may be NULL: zero),
+ *     as autograd gives them on the composition above, lp's path through x included.  Nothing is saved by the forward: the backward
+ *     takes the same alpha, beta, first_object, seed, draw (and u_dev) and re-evaluates the pixel.
+ *   _uniforms_host_f32: the generator's u for the same arguments into HOST memory u_out_host [n][pix]; needs no GPU.
+ * n * pix <= 2^31 - 1; first_object >= 0. */
+int ctpvae_tn_head_fwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                           unsigned long long seed, unsigned draw, const float *u_dev, float *x_out_dev, float *lp_sum_out_dev,
+                           float *lp_elem_out_dev, ctpvae_stream_t stream);
+int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                           unsigned long long seed, unsigned draw, const float *u_dev, const float *g_x_dev, const float *g_lp_dev,
+                           float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream);
+int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host);
+
 #ifdef __cplusplus
 }
 #endif
