@@ -12,5 +12,6 @@ from .fbp import iradon, iradon_all  # noqa: F401
 from .recon import crop, evaluate_sinogram, recon, siddon_backproject  # noqa: F401
 from .mcmc import hmc_sample  # noqa: F401
 from .output_head import head_uniforms, truncated_normal_head  # noqa: F401
+from .latents import latent_draws, normal_latents  # noqa: F401
 
 __version__ = "0.2.0"

@@ -157,6 +157,12 @@ SIGNATURES = {
     "ctpvae_tn_head_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
     "ctpvae_tn_head_uniforms_host_f32": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp]),
+    "ctpvae_latent_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint,
+                                       ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_latent_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint,
+                                       ctypes.c_uint, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_latent_draws_host_f32": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                              _vp]),
 }
 
 _lib = None

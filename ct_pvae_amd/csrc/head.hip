@@ -46,11 +46,12 @@
 #include "common.h"
 #include "loglik_math.h"
 #include "philox.h"
+#include "quad_io.h"
 
 namespace ctpvae {
 
 constexpr unsigned kHeadTag = 0x544E48u;     // "TNH": the fourth counter word (hmc.hip: 0x484D43, poisson.hip: 0)
-constexpr int kHeadFwdThreads = 1024;
+constexpr int kHeadFwdThreads = kObjectSumThreads;
 constexpr int kHeadBwdThreads = 256;
 constexpr float kHeadEps = 1.1920928955078125e-07f;    // FLT_EPSILON, positive_range's offset
 constexpr float kHeadPLo = 1e-7f;
@@ -65,11 +66,6 @@ __host__ __device__ inline Philox4 head_block(unsigned long long blk, unsigned d
 {
     return philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), draw, kHeadTag, k0, k1);
 }
-// word k (0 .. 3) of a block, without indexing the array by a run-time value
-__host__ __device__ inline unsigned head_word(const Philox4 &b, unsigned k)
-{
-    return k == 0 ? b.w[0] : (k == 1 ? b.w[1] : (k == 2 ? b.w[2] : b.w[3]));
-}
 // the uniforms of the four pixels e .. e+3 (one block when e is a multiple of 4, two otherwise)
 __device__ __forceinline__ void head_uniforms4(unsigned long long e, unsigned draw, unsigned k0, unsigned k1, float (&u)[4])
 {
@@ -78,7 +74,7 @@ __device__ __forceinline__ void head_uniforms4(unsigned long long e, unsigned dr
     Philox4 B = A;
     if (s != 0) B = head_block((e >> 2) + 1, draw, k0, k1);
 #pragma unroll
-    for (unsigned j = 0; j < 4; ++j) u[j] = head_u24(s + j < 4 ? head_word(A, s + j) : head_word(B, s + j - 4));
+    for (unsigned j = 0; j < 4; ++j) u[j] = head_u24(s + j < 4 ? philox_word(A, s + j) : philox_word(B, s + j - 4));
 }
 
 struct TnPixel {
@@ -122,30 +118,6 @@ struct HeadRng {
     const float *u_in;                // [n][pix] or nullptr
 };
 
-__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-__device__ __forceinline__ void st4(float *p, const float (&v)[4]) { *reinterpret_cast<float4 *>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-// the pixels i .. i+cnt-1 of an array; the rest of the quad reads `fill`
-__device__ __forceinline__ void head_load(const float *p, size_t i, int cnt, bool vec, float fill, float (&v)[4])
-{
-    if (vec && cnt == 4) {
-        const float4 q = ld4(p + i);
-        v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[i + j] : fill;
-    }
-}
-__device__ __forceinline__ void head_store(float *p, size_t i, int cnt, bool vec, const float (&v)[4])
-{
-    if (vec && cnt == 4) {
-        st4(p + i, v);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < cnt) p[i + j] = v[j];
-    }
-}
-
 __global__ __launch_bounds__(kHeadFwdThreads) void tn_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
                                                                       int pix, HeadRng rng, int ptr_aligned, float *__restrict__ x_out,
                                                                       float *__restrict__ lp_sum, float *__restrict__ lp_elem)
@@ -161,9 +133,9 @@ __global__ __launch_bounds__(kHeadFwdThreads) void tn_head_fwd_kernel(const floa
         const int cnt = pix - r < 4 ? pix - r : 4;
         const size_t i = base + r;
         float al[4], be[4], u[4], x[4], lp[4];
-        head_load(alpha, i, cnt, vec, 1.0f, al);
-        head_load(beta, i, cnt, vec, 1.0f, be);
-        if (rng.u_in != nullptr) head_load(rng.u_in, i, cnt, vec, 0.5f, u);
+        quad_load(alpha, i, cnt, vec, 1.0f, al);
+        quad_load(beta, i, cnt, vec, 1.0f, be);
+        if (rng.u_in != nullptr) quad_load(rng.u_in, i, cnt, vec, 0.5f, u);
         else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -171,19 +143,12 @@ __global__ __launch_bounds__(kHeadFwdThreads) void tn_head_fwd_kernel(const floa
             x[j] = px.x;
             lp[j] = j < cnt ? px.lp : 0.0f;
         }
-        head_store(x_out, i, cnt, vec, x);
-        if (lp_elem != nullptr) head_store(lp_elem, i, cnt, vec, lp);
+        quad_store(x_out, i, cnt, vec, x);
+        if (lp_elem != nullptr) quad_store(lp_elem, i, cnt, vec, lp);
         acc += ((lp[0] + lp[1]) + lp[2]) + lp[3];
     }
-    const float w = wave_sum(acc);
-    if ((t & 63) == 0) wsum[t >> 6] = w;
-    __syncthreads();
-    if (t == 0) {
-        float s = wsum[0];
-#pragma unroll
-        for (int k = 1; k < kHeadFwdThreads / 64; ++k) s += wsum[k];
-        lp_sum[o] = s;
-    }
+    const float s = object_sum_1024(acc, wsum, t);
+    if (t == 0) lp_sum[o] = s;
 }
 
 __global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
@@ -197,11 +162,11 @@ __global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const floa
     const size_t i = (size_t)i0;
     const bool vec = ptr_aligned != 0;
     float al[4], be[4], u[4], gx[4], ga[4], gb[4];
-    head_load(alpha, i, cnt, vec, 1.0f, al);
-    head_load(beta, i, cnt, vec, 1.0f, be);
-    if (rng.u_in != nullptr) head_load(rng.u_in, i, cnt, vec, 0.5f, u);
+    quad_load(alpha, i, cnt, vec, 1.0f, al);
+    quad_load(beta, i, cnt, vec, 1.0f, be);
+    if (rng.u_in != nullptr) quad_load(rng.u_in, i, cnt, vec, 0.5f, u);
     else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
-    if (g_x != nullptr) head_load(g_x, i, cnt, vec, 0.0f, gx);
+    if (g_x != nullptr) quad_load(g_x, i, cnt, vec, 0.0f, gx);
     else gx[0] = gx[1] = gx[2] = gx[3] = 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -220,8 +185,8 @@ __global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const floa
         ga[j] = gloc * px.dloc;
         gb[j] = gscale * px.dscale;
     }
-    head_store(g_alpha, i, cnt, vec, ga);
-    head_store(g_beta, i, cnt, vec, gb);
+    quad_store(g_alpha, i, cnt, vec, ga);
+    quad_store(g_beta, i, cnt, vec, gb);
 }
 
 static int head_check(const char *what, const void *alpha, const void *beta, int n, int pix, long long first_object)
@@ -290,7 +255,7 @@ int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, uns
     const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     for (long long i = 0; i < total; ++i) {
         const unsigned long long e = e0 + (unsigned long long)i;
-        u_out_host[i] = head_u24(head_word(head_block(e >> 2, draw, k0, k1), (unsigned)e & 3u));
+        u_out_host[i] = head_u24(philox_word(head_block(e >> 2, draw, k0, k1), (unsigned)e & 3u));
     }
     return CTPVAE_OK;
 }

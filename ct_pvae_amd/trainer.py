@@ -37,6 +37,7 @@ from .create_masks import create_all_masks
 from .fbp import iradon_all
 from .forward_functions import num_proj_pix
 from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
+from .latents import normal_latents
 from .output_head import truncated_normal_head
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -233,15 +234,22 @@ def kl_normal_std(loc, scale):
 # ---------------------------------------------------------------------------------------------------------
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
-                        use_normal=True, model="rotate", noise="gaussian", fused_head=None):
+                        use_normal=True, model="rotate", noise="gaussian", fused_head=None, fused_latents=None):
     """fused_head: None -- the output distribution is the chain of torch operations below, its uniforms from torch's global
     generator -- or (seed, draw, first_object): sample, log-density and its per-object sum come from ONE launch
-    (output_head.truncated_normal_head, csrc/head.hip), the uniforms from Philox keyed by those three; --normal only."""
+    (output_head.truncated_normal_head, csrc/head.hip), the uniforms from Philox keyed by those three; --normal only.
+    fused_latents: None -- the Normal latents and their KL term are the chain of torch operations below, the draws from torch's
+    global generator -- or (seed, draw, first_object): per skip level ONE launch gives the ns samples and the per-object KL
+    (latents.normal_latents, csrc/latent.hip), the draws from Philox keyed by those three, the level and the sample; first_object is
+    the offset of this call's objects in the GLOBAL batch; --normal only, not with deterministic."""
     if fused_head is not None and not use_normal:
         raise ValueError("fused_head is the TruncatedNormal output head: it needs use_normal=True (the Beta head is not fused)")
+    if fused_latents is not None and (not use_normal or deterministic):
+        raise ValueError("fused_latents is the Normal latent block: it needs use_normal=True and deterministic=False (the Beta latents "
+                         "are not fused)")
     skips = model_encode(input_encode / 300)
     q = None
-    if not deterministic:
+    if not deterministic and fused_latents is None:
         q = []
         for sk in skips:
             loc, log_scale = sk.chunk(2, dim=1)
@@ -256,6 +264,14 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     B = input_encode.shape[0]
     if deterministic:
         q_sample = skips
+    elif fused_latents is not None:
+        seed, draw, first_object = fused_latents
+        q_sample, level_kl = [], []
+        for level, sk in enumerate(skips):
+            z, kl_level = normal_latents(sk.contiguous(), ns=ns, seed=seed, draw=draw, level=level, first_object=first_object,
+                                         sqrt_reg=sqrt_reg)
+            q_sample.append(z)
+            level_kl.append(kl_level)
     elif use_normal:
         q_sample = [loc.repeat(ns, 1, 1, 1) + scale.repeat(ns, 1, 1, 1) * torch.randn((ns * B,) + tuple(loc.shape[1:]),
                                                                                       device=loc.device, dtype=loc.dtype)
@@ -289,6 +305,8 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     recon = output_sample[(ns - 1) * B:]
     if deterministic:
         kl = lp.new_zeros(B)
+    elif fused_latents is not None:
+        kl = sum(level_kl[2:], level_kl[1]) if len(level_kl) > 1 else lp.new_zeros(B)   # ascending level; the input level is unused
     elif use_normal:
         kl = sum(kl_normal_std(loc, scale).sum(dim=(1, 2, 3)) for loc, scale in q[1:])   # the input level is unused
     else:                                                           # prior Beta(0.5, 0.5), ctvae/main_ct_vae.py:372
@@ -320,6 +338,8 @@ class PVAETrainer:
         self.args, self.dev = args, device
         if getattr(args, "fused_head", False) and not args.use_normal:
             raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
+        if getattr(args, "fused_latents", False) and (not args.use_normal or args.deterministic):
+            raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
         self.world, self.rank, _ = sharding.env_world()
         self.sqrt_reg = EPS32
         # the nets' shapes are static: --miopen_find lets MIOpen search its convolution algorithms once (14.9 -> 11.5 ms
@@ -439,12 +459,17 @@ class PVAETrainer:
         fused = None
         if getattr(a, "fused_head", False):
             fused = (a.head_seed, self.iter, self.rank * (1 if a.deterministic else a.ns) * input_encode.shape[0])
+        # --fused_latents: the same seed and draw; the latents' objects are counted in the GLOBAL batch (the sample index is a counter
+        # word of its own), so their draws are the same at every world size
+        fused_lat = None
+        if getattr(a, "fused_latents", False):
+            fused_lat = (a.head_seed, self.iter, sharding.shard_range(a.batch_size, self.rank, self.world)[0])   # _batch's lo
         loss_vec, kl, loglik, _ = find_loss_vae_unsup(proj_sample, mask, input_encode, self.enc, self.dec, pnm_i,
                                                       self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
                                                       theta=self.theta_host, angles_i=angles_i, pad=self.pad,
                                                       deterministic=a.deterministic, use_normal=a.use_normal,
                                                       model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
-                                                      fused_head=fused)
+                                                      fused_head=fused, fused_latents=fused_lat)
         # ctvae/main_ct_vae.py:478 reduce_mean(loss_M_VAE) / 1e5 = mean_b(KL term) - loglik, where loglik already sums
         # over the batch.  Written so that the ranks' losses ADD UP to the global one (gradients are summed over ranks):
         # each rank contributes its objects' KL / global_B and its own objects' log-likelihood.
@@ -613,10 +638,14 @@ def get_args(argv=None):
     p.add_argument("--fused_head", action="store_true",
                    help="sample the TruncatedNormal output and sum its log-density in one launch (csrc/head.hip), with Philox uniforms "
                         "keyed by (--head_seed, step index, object) instead of torch's global generator; needs --normal")
+    p.add_argument("--fused_latents", action="store_true",
+                   help="sample the Normal latents and sum their KL term in one launch per skip level (csrc/latent.hip), with Philox "
+                        "draws keyed by (--head_seed, step index, level, sample, global object) instead of torch's global generator; "
+                        "needs --normal, not with --det")
     p.add_argument("--reproducible", action="store_true",
                    help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
                         "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")
-    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's uniforms")
+    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's uniforms and of --fused_latents' draws")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")
@@ -644,6 +673,8 @@ def get_args(argv=None):
     args = p.parse_args(argv)
     if args.fused_head and not args.use_normal:
         raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
+    if args.fused_latents and (not args.use_normal or args.deterministic):
+        raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
     return args
 
 

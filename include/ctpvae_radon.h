@@ -692,6 +692,32 @@ int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n,
                            float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream);
 int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host);
 
+/* ---- the P-VAE's Normal latent block at one skip level (ctvae/helper_functions.py:247-252, :267, :325-327): the ns reparameterised
+ * samples, the KL term against N(0, 1) and its per-object sum in ONE launch, their gradients in one more (csrc/latent.hip states the
+ * function, the order of the sum and the layout of the random numbers).  skip_dev [B][2][len]: the encoder's output at the level,
+ * len = C * H * W; the first half of an object is loc, the second log_scale, fp32.
+ *   scale = pr(log_scale) + sqrt_reg, pr(t) = t >= 1 ? t : exp(t - 1) + FLT_EPSILON
+ *   z[s * B + b][i] = loc + scale * eps(s, b, i);   kl[b][i] = 0.5 (scale^2 + loc^2 - 1) - log scale;   KL[b] = sum_i kl[b][i]
+ * eps of element i of object b, sample s, comes from word e & 3 of Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), draw,
+ * 0x4C000000 | level << 16 | s), key = seed), e = (first_object + b) * len + i:  t = (((w >> 7) & 0xFFFFFF) + 0.5f) * 2^-25,
+ * eps = bit 31 of w ? ndtri(t) : -ndtri(t).  A batch cut into calls with first_object draws what the whole batch draws.  A non-null
+ * eps_dev [ns * B][len] replaces the generator (tests).
+ *   _fwd_f32: z_out_dev [ns * B][len], kl_sum_out_dev [B] (the sum of an object's kl in the fixed order of csrc/latent.hip: the same
+ *     bits whatever B and first_object), kl_elem_out_dev [B][len] or NULL, eps_out_dev [ns * B][len] or NULL (the draws used).
+ *   _bwd_f32: g_skip_out_dev [B][2][len] for the cotangents g_z_dev [ns * B][len] and g_kl_dev [B] (either may be NULL: zero).  Nothing
+ *     is saved by the forward: the backward takes the same skip, sqrt_reg, first_object, seed, draw, level (and eps_dev).
+ *   _draws_host_f32: the signed tail probability v = bit 31 ? -t : +t of the same arguments into HOST memory v_out_host [ns][n][len]
+ *     (eps = copysign(-ndtri(|v|), v)); needs no GPU and evaluates no quantile.
+ * ns * B * len <= 2^31 - 1; 1 <= ns <= 65535; level <= 255; first_object >= 0. */
+int ctpvae_latent_fwd_f32(const float *skip_dev, int B, int len, int ns, float sqrt_reg, long long first_object, unsigned long long seed,
+                          unsigned draw, unsigned level, const float *eps_dev, float *z_out_dev, float *kl_sum_out_dev,
+                          float *kl_elem_out_dev, float *eps_out_dev, ctpvae_stream_t stream);
+int ctpvae_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, float sqrt_reg, long long first_object, unsigned long long seed,
+                          unsigned draw, unsigned level, const float *eps_dev, const float *g_z_dev, const float *g_kl_dev,
+                          float *g_skip_out_dev, ctpvae_stream_t stream);
+int ctpvae_latent_draws_host_f32(int n, int len, int ns, long long first_object, unsigned long long seed, unsigned draw, unsigned level,
+                                 float *v_out_host);
+
 #ifdef __cplusplus
 }
 #endif
