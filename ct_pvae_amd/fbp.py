@@ -17,6 +17,7 @@ __all__ = ["iradon", "iradon_all", "ramp_filter"]
 
 _CACHE = {}
 _CACHE_MAX = 32
+_MAX_BINS = 64 * 1024 // (2 * 8)   # fbp_filter_kernel: 2 * P doubles of LDS, 64 KiB per workgroup
 
 
 def _cached(key, make):
@@ -50,11 +51,23 @@ def iradon(sinogram, theta, x_size, y_size, filter_1d, *, tomopy_geometry=False)
     if num_angles != A:
         # same exception type and wording as ctvae/fbp_tensorflow.py:43-45
         raise ValueError("The given ``theta`` does not match the number of projections in ``radon_image``.")
+    if P < 2:
+        raise ValueError(f"iradon interpolates between detector bins and needs at least 2 of them (got {P})")
+    if P > _MAX_BINS:   # a limit of the build, not a malformed call (csrc/fbp.hip: ctpvae_fbp_filter_f64 holds the same line)
+        raise _lib.RadonLibraryError(f"iradon: {P} detector bins do not fit LDS (the filter kernel keeps a row and the filter's "
+                                     f"kernel there: at most {_MAX_BINS} bins)")
     dev = sinogram.device
     filt = np.asarray(filter_1d.detach().cpu() if isinstance(filter_1d, torch.Tensor) else filter_1d)
     filt = filt.reshape(-1)
     if filt.shape[0] != P:
         raise ValueError(f"filter_1d must hold num_proj_pix={P} values (got {filt.shape[0]})")
+    X, Y = int(x_size), int(y_size)
+    geom = ((X - 1) / 2.0, (Y - 1) / 2.0, (P - 1) / 2.0) if tomopy_geometry else (X / 2.0, Y / 2.0, P / 2.0)
+    if B == 0:   # an empty batch is an empty result, as the reference's op chain gives: no table, no launch
+        none = sinogram.new_empty((0,), dtype=torch.float64)
+        if sinogram.requires_grad and torch.is_grad_enabled():
+            return _IRadon.apply(sinogram, none, none, none, none, X, Y, geom)
+        return _iradon_forward(sinogram, none, none, none, X, Y, geom)
     hker = _cached(("hker", filt.tobytes(), str(filt.dtype), str(dev)), lambda: torch.from_numpy(
         np.ascontiguousarray(np.fft.ifft(filt.astype(np.complex128)).real)).to(dev))
     if isinstance(theta, torch.Tensor) and theta.device.type == "cuda":
@@ -69,8 +82,6 @@ def iradon(sinogram, theta, x_size, y_size, filter_1d, *, tomopy_geometry=False)
             return torch.cos(th).contiguous(), torch.sin(th).contiguous()
 
         cos_t, sin_t = _cached(("trig", th_np.tobytes(), str(dev)), make)
-    X, Y = int(x_size), int(y_size)
-    geom = ((X - 1) / 2.0, (Y - 1) / 2.0, (P - 1) / 2.0) if tomopy_geometry else (X / 2.0, Y / 2.0, P / 2.0)
     if sinogram.requires_grad and torch.is_grad_enabled():
         # the transposed filter: hker reversed, hker[(P - n) % P]
         hker_t = _cached(("hker_t", filt.tobytes(), str(filt.dtype), str(dev)), lambda: torch.roll(torch.flip(hker, (0,)), 1, 0).contiguous())
@@ -82,6 +93,8 @@ def _iradon_forward(sinogram, hker, cos_t, sin_t, X, Y, geom):
     lib = _lib.load()
     B, A, P = sinogram.shape
     dev = sinogram.device
+    if B == 0:
+        return torch.empty((0, X, Y), dtype=torch.float64, device=dev)
     sino = sinogram.to(torch.float64).contiguous()
     filtered = _fwd._new_output(sino.shape, sino.dtype, sino.device)
     recon = _fwd._new_output((B, X, Y), torch.float64, dev)
@@ -109,6 +122,8 @@ class _IRadon(torch.autograd.Function):
         lib = _lib.load()
         hker_t, cos_t, sin_t = ctx.saved_tensors
         (B, A, P), X, Y = ctx.shape
+        if B == 0:
+            return torch.empty((0, A, P), dtype=ctx.in_dtype, device=grecon.device), None, None, None, None, None, None, None
         g = grecon.to(torch.float64).contiguous()
         gfilt = _fwd._new_output((B, A, P), torch.float64, g.device)
         gsino = _fwd._new_output(gfilt.shape, gfilt.dtype, gfilt.device)

@@ -1231,7 +1231,8 @@ def test_long_batches_are_launched_in_chunks():
 
 def test_empty_batch_is_an_empty_result():
     """A batch of zero objects projects to zero sinograms (what the TensorFlow op chain gives), forward and backward,
-    through the raw operator, the public function and the likelihood caller -- no launch, no error."""
+    through the raw operator, the public function and the likelihood caller -- no launch, no error.  iradon likewise: no
+    sinograms reconstruct to no images (tests/test_gpu_fbp.py has the gradient and both geometries)."""
     d = dev()
     theta = np.linspace(0, np.pi, 6, endpoint=False)
     plan = RotatePlan(theta, 32, 32, True, d)
@@ -1245,6 +1246,8 @@ def test_empty_batch_is_an_empty_result():
     lp = cp.calculate_log_prob_M_given_R(x, torch.empty((0, 6), device=d), torch.empty((0, 6, plan.PW), device=d), 1e3, 1e-7,
                                          theta=theta, pad=True)
     assert tuple(lp.shape) == (0, 6, plan.PW, 1)
+    rec = cp.iradon(torch.empty((0, 6, plan.PW), device=d), theta, 32, 32, np.ones(plan.PW))
+    assert tuple(rec.shape) == (0, 32, 32) and rec.dtype is torch.float64
 
 
 def test_bad_shapes_raise():
