@@ -81,6 +81,7 @@ SIGNATURES = {
     "ctpvae_rotate_plan_build_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp,
                                               _vp]),
     "ctpvae_rotate_fwd_planned_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_rotate_fwd_planned_form": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "ctpvae_rotate_fwd_planned_loglik_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp,
                                                       _c_float, _vp, _vp, _vp, _vp]),
     "ctpvae_rotate_bwd_planned_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),

@@ -375,6 +375,29 @@ __global__ __launch_bounds__(64) void rotate_class_list_kernel(int A, FwdLayout 
 // 64 r + l, its plan angle and its rank among the entries of class c; the ai-th angle of the class is then one ballot
 // + readlane away.
 constexpr int kSelRounds = 4;
+// The walk of one task's row groups, shared by the two forms of the kernel (this one and rotate_fwd_planned_kernel_few) so that both
+// add a ray's rows in the same order.  In scope: lds, ng (> 0, wave-uniform), p, st, q0..q3 (index vectors of groups 0..3, q0 already
+// gathered into va and reloaded), va, vb, acc.
+// (round 4: the task's last group issues nothing behind it -- the gathers of a group past the last were ~7 % of the
+// launch's LDS instructions)
+#define CTPVAE_PSTEP(LAST, QN, VN, VC, LOADNEXT)                                                   \
+                if (LAST >= ng) {   /* VC is the last group: added behind the loop (see cplan_walk.h cwalk) */ \
+                    _Pragma("unroll") for (int e = 0; e < 8; ++e) vt[e] = VC[e];                    \
+                    break;                                                                         \
+                }                                                                                  \
+                gather8(lds, QN, VN);                                                              \
+                LOADNEXT;                                                                          \
+                __builtin_amdgcn_sched_barrier(0);                                                 \
+                _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += VC[e];
+#define CTPVAE_FWD_WALK_U16                                                                        \
+            vec_t vt[8];                                                                           \
+            for (int n = 0;; n += 4) {                                                             \
+                CTPVAE_PSTEP(n + 1, q1, vb, va, q1 = p[st])                 /* adds group n */     \
+                CTPVAE_PSTEP(n + 2, q2, va, vb, q2 = p[2 * st])             /* group n + 1 */      \
+                CTPVAE_PSTEP(n + 3, q3, vb, va, q3 = p[3 * st])             /* group n + 2 */      \
+                CTPVAE_PSTEP(n + 4, q0, va, vb, (p += 4 * st, q0 = p[0]))   /* group n + 3 */      \
+            }                                                                                      \
+            _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += vt[e];
 template <int NS, bool EPI, bool SEL>
 __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel(const float *__restrict__ img, PlanGeom g, FwdLayout L,
                                                                   const char *__restrict__ plan, int wgs_per_slice,
@@ -604,27 +627,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel(const float *_
                     if (n + 4 >= ng) break;
                 }
             } else {
-            // (round 4: the task's last group issues nothing behind it -- the gathers of a group past the last were ~7 % of the
-            // launch's LDS instructions)
-#define CTPVAE_PSTEP(LAST, QN, VN, VC, LOADNEXT)                                                   \
-                if (LAST >= ng) {   /* VC is the last group: added behind the loop (see cplan_walk.h cwalk) */ \
-                    _Pragma("unroll") for (int e = 0; e < 8; ++e) vt[e] = VC[e];                    \
-                    break;                                                                         \
-                }                                                                                  \
-                gather8(lds, QN, VN);                                                              \
-                LOADNEXT;                                                                          \
-                __builtin_amdgcn_sched_barrier(0);                                                 \
-                _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += VC[e];
-            vec_t vt[8];
-            for (int n = 0;; n += 4) {
-                CTPVAE_PSTEP(n + 1, q1, vb, va, q1 = p[st])                 // adds group n
-                CTPVAE_PSTEP(n + 2, q2, va, vb, q2 = p[2 * st])             // group n + 1
-                CTPVAE_PSTEP(n + 3, q3, vb, va, q3 = p[3 * st])             // group n + 2
-                CTPVAE_PSTEP(n + 4, q0, va, vb, (p += 4 * st, q0 = p[0]))   // group n + 3
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc += vt[e];
-#undef CTPVAE_PSTEP
+                CTPVAE_FWD_WALK_U16
             }
         }
         if ((unsigned)cur.j < (unsigned)g.PW) {
@@ -644,6 +647,134 @@ __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel(const float *_
     }
     CTPVAE_PSTAMP(3);
 }
+
+// The FEW form of the forward above, for the launches that are mostly prologue: dense (all plan angles, no epilogue), ONE part of
+// pieces, not affine, a unit that stage_unit_pow2_m serves in one batch of loads (launch_fwd_planned's rule, fwd_few_ok).  A launch of
+// one round of workgroups costs ~2 us of launch floor plus ~4 us from a workgroup's start to its staged unit, and that prologue costs
+// the instructions its 16 waves issue on 4 SIMDs: the general kernel carries every staging form, the three-part
+// piece list, the affine shape and the division fallbacks in front of its barrier.  Here the launch's constants are made on the host
+// (final table pointers, strides, shifts, division words), the piece is decoded for one part by multiplications alone, the wave number
+// is a SCALAR -- so a wave's first task is set up by scalar loads (class count, angle, range: lgkmcnt, not queued with the row loads)
+// that end in one vector address per lane, AHEAD of the unit's row requests (requesting the rows first measured 0.19 us slower at the
+// headline batch, profiles/r13_fwd_few_ab.txt) --, waves without a task branch around all of it, and the unit goes straight through
+// stage_unit_pow2_m.  Behind the barrier it is the kernel above: the same walk (CTPVAE_FWD_WALK_U16), later tasks from the LDS counter,
+// the same stores -- the same bits.
+struct FwdFewArgs {
+    const int *clist;           // class 0's (count, angles...); class 1's list starts A1 ints behind it
+    const unsigned *inv_ncls;   // div_magic of the two counts
+    const int *rng;
+    const uint4 *idx;
+    int A, A1, rows, cs, src_stride, pitch, zero, PW, nJB;
+    int st, ast;                // index strides in uint4: one row group (PWpad), one angle (Galloc * PWpad)
+    int G, wgs, S, units, slice;   // task groups per class, pieces per unit (2 G >= 2), slices, units, floats per slice
+    unsigned inv_wgs;           // div_magic(wgs); the host checked the range (small_div)
+};
+template <int NS>
+__global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel_few(const float *__restrict__ img, float *__restrict__ sino, FwdFewArgs k)
+{
+    typedef typename SliceVec<NS>::type vec_t;
+    extern __shared__ float lds[];
+    // the piece (unit, class, task group): octets of units as in the kernel above, the partial last octet unit-major
+    const unsigned q = blockIdx.x, per8 = 8u * (unsigned)k.wgs;
+    const unsigned octet = div_by_magic(q >> 3, k.inv_wgs), rem = q - octet * per8;
+    int u, wg;
+    if ((int)(octet + 1) * 8 <= k.units) {
+        wg = rem >> 3;
+        u = octet * 8 + (rem & 7);
+    } else {
+        const unsigned ru = div_by_magic(rem, k.inv_wgs);
+        u = octet * 8 + ru;
+        wg = rem - ru * k.wgs;
+    }
+    const int s = u * NS;
+    const bool has2 = NS == 2 && s + 1 < k.S;
+    const int c = wg & 1, gi = wg >> 1;
+    const int lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float *im = img + (size_t)s * k.slice;
+    CTPVAE_PSTAMP(0);
+
+    const int *clist = k.clist + c * k.A1;
+    const int ncls = clist[0], ntask = ncls * k.nJB;
+    const unsigned inv_ncls = k.inv_ncls[c];
+#ifdef CTPVAE_TUNE_NOIDX
+    const size_t st = 0;
+#else
+    const size_t st = (size_t)k.st;
+#endif
+    struct Task {
+        bool valid;
+        int a, j, ng;
+        const uint4 *p;
+        uint4 q0, q1, q2, q3;
+    };
+    auto fill = [&](Task &t, int m) {   // task m of the class's (bin block, angle) list: its range and first four index vectors
+        const int jb = (int)div_by_magic((unsigned)m, inv_ncls), ai = m - jb * ncls;
+        t.a = clist[1 + ai];
+        const int first = k.rng[(t.a * k.nJB + jb) * 2], last = kRngBias - k.rng[(t.a * k.nJB + jb) * 2 + 1];
+        const int g0 = last >= first ? first : 0;
+        t.ng = last >= first ? last - first + 1 : 0;
+        t.j = lane_to_bin(k.PW, jb, lane);
+        t.p = k.idx + ((size_t)t.a * k.ast + (size_t)g0 * k.st + jb * 64) + lane;
+        t.q0 = t.p[0];
+        t.q1 = t.p[st];
+        t.q2 = t.p[2 * st];
+        t.q3 = t.p[3 * st];
+        t.p += 4 * st;
+    };
+    Task cur;
+    const int m0 = wave * k.G + gi;
+    cur.valid = m0 < ntask;
+    if (cur.valid) fill(cur, m0);   // (a scalar branch: waves without a task skip the chain, and no record is zeroed for them)
+    int *next_task = reinterpret_cast<int *>(lds + (k.zero + 1) * NS);
+    if (threadIdx.x == 0) *next_task = nwaves;
+
+    {
+        const float *srcs[NS];
+        srcs[0] = im;
+        if constexpr (NS == 2) srcs[1] = im + (has2 ? (size_t)k.slice : 0);
+        if (c == 0) stage_unit_pow2_m<NS, 8 / NS, true>(lds, srcs, k.rows, k.cs, k.src_stride, k.pitch, lane, wave, nwaves, [] {});
+        else stage_unit_pow2_m<NS, 8 / NS, false>(lds, srcs, k.rows, k.cs, k.src_stride, k.pitch, lane, wave, nwaves, [] {});
+    }
+    if (threadIdx.x < NS) lds[k.zero * NS + threadIdx.x] = 0.0f;
+    CTPVAE_PSTAMP(1);
+    __syncthreads();
+    CTPVAE_PSTAMP(2);
+
+    while (cur.valid) {
+        int m = 0;
+        if (lane == 0) m = atomicAdd(next_task, 1);
+        Task nxt;
+        {
+            const int mn = __builtin_amdgcn_readfirstlane(m) * k.G + gi;
+            nxt.valid = mn < ntask;
+            if (nxt.valid) fill(nxt, mn);
+        }
+        const int ng = __builtin_amdgcn_readfirstlane(cur.ng);
+        const uint4 *p = cur.p;
+        vec_t acc = 0.0f;
+        if (ng > 0) {
+            uint4 q0 = cur.q0, q1 = cur.q1, q2 = cur.q2, q3 = cur.q3;
+            vec_t va[8], vb[8];
+            gather8(lds, q0, va);
+            q0 = p[0];
+            CTPVAE_FWD_WALK_U16
+        }
+        if ((unsigned)cur.j < (unsigned)k.PW) {
+            const size_t o = ((size_t)s * k.A + cur.a) * k.PW + cur.j;
+            if constexpr (NS == 1) {
+                sino[o] = acc;
+            } else {
+                sino[o] = acc.x;
+                if (has2) sino[o + (size_t)k.A * k.PW] = acc.y;
+            }
+        }
+        cur = nxt;
+    }
+    CTPVAE_PSTAMP(3);
+}
+#undef CTPVAE_FWD_WALK_U16
+#undef CTPVAE_PSTEP
 
 // four byte taps of one dword -> four LDS byte offsets inside a cotangent row (SDWA: select a byte, shift by
 // log2(bytes per cell): 2, or 3 when two slices are interleaved as float2)
@@ -1169,8 +1300,6 @@ int ctpvae_rotate_plan_build_f32(const float *T8_dev, const float *Tinv8_dev, in
     return CTPVAE_OK;
 }
 
-// sel_dev == nullptr: all A angles of the plan; otherwise the n_sel plan angles sel_dev[0..n_sel) (device int32), in
-// that order, are projected -- the launch shape is then sized for n_sel angles.
 // Launches of several rounds (round 4, tools/sweep_fwd.py at 100 to 400 slices x 20 / 90 / 180 angles, profiles/r04_sweep_G.txt):
 // a round of workgroups costs its fill and tasks plus ~2.5 us of ramp and drain (kRoundKb in the model's KB-per-CU currency), and
 // a launch of r.x rounds takes nearer to ceil(r.x) than to r.x of them.  Fitted so that the model picks the measured best task
@@ -1182,20 +1311,26 @@ static inline double launch_rounds(long long wgs)
     return whole > 1.0 ? real + 0.75 * (whole - real) : 1.0;
 }
 
-static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *fwd_plan_dev,
-                              float *sino_dev, const LogLikEpilogue &epi, const int *sel_dev, int n_sel,
-                              ctpvae_stream_t stream)
+// The shape of a planned forward launch, computed WITHOUT launching (ctpvae_rotate_fwd_planned_form asks it for the kernel form alone)
+struct FwdShape {
+    PlanGeom g;
+    FwdLayout L;
+    int ns, affine, waves, units, wgs_per_slice, units1, wgs2, units2, wgs3, small_div;
+    long long grid;
+    size_t shmem;
+};
+// has_sel: the launch projects n_sel of the plan's angles (the shape is then sized for n_sel angles)
+static int fwd_planned_shape(int S, int H, int W, int PH, int PW, int A, bool has_sel, int n_sel, FwdShape &sh)
 {
-    CTPVAE_REQUIRE(img_dev && fwd_plan_dev && sino_dev, "rotate_fwd_planned: null pointer");
     CTPVAE_REQUIRE(S > 0, "rotate_fwd_planned: need at least one slice");
     if (int rc = check_plan_geom("rotate_fwd_planned", H, W, PH, PW, 0, 0, A)) return rc;
-    CTPVAE_REQUIRE(sel_dev == nullptr || (n_sel >= 1 && n_sel <= 64 * kSelRounds),
+    CTPVAE_REQUIRE(!has_sel || (n_sel >= 1 && n_sel <= 64 * kSelRounds),
                    "rotate_fwd_planned: an angle subset holds 1..%d angles (got %d); build a plan for larger ones",
                    64 * kSelRounds, n_sel);
     const PlanGeom g{H, W, PH, PW, 0, 0, A};
     CTPVAE_REQUIRE(fwd_plan_fits(g), "rotate_fwd_planned: a %dx%d slice does not fit the plan's LDS image", H, W);
     const FwdLayout L = fwd_layout(g);
-    const int A_run = sel_dev ? n_sel : A;      // angles this launch projects
+    const int A_run = has_sel ? n_sel : A;      // angles this launch projects
     const int T = A_run * L.nJB;   // (angle, bin block) tasks per slice
     // Launch shape.  What a launch costs is the bytes its busiest CU pulls through its L2->CU path (DESIGN.md section
     // 6): per workgroup one staged unit -- a slice, or a PAIR of slices interleaved as float2, whose index stream, unpack
@@ -1249,7 +1384,7 @@ static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH,
             }
         }
         // dense launches of plans larger than an XCD's L2 only (knob AFFINE: 0 never, 1 whenever the shape allows)
-        const bool can = !sel_dev && T >= 8 && best_aff > 0.0;
+        const bool can = !has_sel && T >= 8 && best_aff > 0.0;
         if (can && knob(kKnobAffine) != 0 && (knob(kKnobAffine) == 1 || (plan_kb > 3072.0 && best_aff < best))) {
             affine = 1;
             ns = ns_aff;
@@ -1303,7 +1438,7 @@ static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH,
     // requested by the waves that run out of tasks first -- was built and measured: bit-equal, its hand-over no cheaper than a
     // fresh workgroup (~3.4 us behind the slowest wave) and its task loop 5 % slower (127 registers, another schedule): removed.
     int units1 = units, wgs2 = wgs_per_slice, units2 = units, wgs3 = wgs_per_slice;
-    if (!affine && !sel_dev && (long long)units * wgs_per_slice > 256 && knob(kKnobMixG) != 0 && knob(kKnobG) <= 0) {
+    if (!affine && !has_sel && (long long)units * wgs_per_slice > 256 && knob(kKnobMixG) != 0 && knob(kKnobG) <= 0) {
         // (a task round is the faster the fewer waves of the CU gather at once: 2.7 us with 6 waves, 4.35 with all 16, at 23 row groups)
         const double t_fresh = 4.4;
         const int Tc = (T + 1) / 2;     // tasks per unit and class
@@ -1404,16 +1539,70 @@ static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH,
 #ifdef CTPVAE_TUNE_STAMPS
     g_pshape[1] = wgs_per_slice, g_pshape[2] = waves, g_pshape[5] = units1, g_pshape[6] = wgs2, g_pshape[7] = units2, g_pshape[8] = wgs3;   // (timing builds: tools/stamp_rounds.hip)
 #endif
+    // divisions by multiplication (div_magic): piece numbers / 8 by the pieces per unit, task numbers by a class's angle count
+    const int small_div = (grid / 8 + 1) * (long long)std::max(wgs_per_slice, std::max(wgs2, wgs3)) < (1ll << 32) && (long long)A * L.nJB * A < (1ll << 32) &&
+                                  knob(kKnobNoMagic) <= 0 ? 1 : 0;
+    sh = FwdShape{g, L, ns, affine, waves, units, wgs_per_slice, units1, wgs2, units2, wgs3, small_div, grid, shmem};
+    return CTPVAE_OK;
+}
+
+// The FEW form (rotate_fwd_planned_kernel_few) serves a launch when it is dense (no angle subset, no epilogue, not affine), its piece
+// list has ONE part, its indices divide by multiplication, the plan is not the SKEW0 experiment's, and the unit goes through
+// stage_unit_pow2_m in one batch of loads: 64 / 128 / 256 columns, rows in fours, (H / 4)(W / 64) blocks <= (8 / ns) per wave, a 16-byte
+// aligned image (slices are H W floats apart, H % 4 == 0: every row is then aligned).  And at most kFewMaxTasks tasks per workgroup:
+// at 54 (B = 50 x 180 angles) the form measured 0.43 us SLOWER than the general kernel (20.16 against 19.73 us, the parent's spread 0.41),
+// at 30 (B = 400 x 20) and below it wins 0.6-0.8 us (profiles/r13_fwd_few_ab.txt) -- a long task loop is another register allocation.
+// Knob FWD_FEW: 0 = never, 1 = whenever the other conditions hold (no task bound), unset = the rule.
+constexpr int kFewMaxTasks = 48;   // three per wave of a 16-wave workgroup
+static bool fwd_few_ok(const FwdShape &sh, bool dense, bool img_aligned16)
+{
+    if (knob(kKnobFwdFew) == 0) return false;
+    const int H = sh.g.H, W = sh.g.W;
+    const int tasks = ceil_div(sh.g.A * sh.L.nJB, sh.wgs_per_slice);   // per workgroup, the classes taken as equal (as the waves rule does)
+    if (knob(kKnobFwdFew) != 1 && tasks > kFewMaxTasks) return false;
+    return dense && !sh.affine && sh.units1 == sh.units && sh.small_div && !sh.L.skew0 && (W == 64 || W == 128 || W == 256) && H % 4 == 0 &&
+           (H / 4) * (W / 64) <= (8 / sh.ns) * sh.waves && img_aligned16;
+}
+
+// sel_dev == nullptr: all A angles of the plan; otherwise the n_sel plan angles sel_dev[0..n_sel) (device int32), in that order
+static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *fwd_plan_dev,
+                              float *sino_dev, const LogLikEpilogue &epi, const int *sel_dev, int n_sel,
+                              ctpvae_stream_t stream)
+{
+    CTPVAE_REQUIRE(img_dev && fwd_plan_dev && sino_dev, "rotate_fwd_planned: null pointer");
+    FwdShape sh;
+    if (int rc = fwd_planned_shape(S, H, W, PH, PW, A, sel_dev != nullptr, n_sel, sh)) return rc;
+    const PlanGeom &g = sh.g;
+    const FwdLayout &L = sh.L;
+    const int ns = sh.ns;
+    if (fwd_few_ok(sh, !sel_dev && !epi.lp, (reinterpret_cast<uintptr_t>(img_dev) & 15) == 0)) {
+        const char *plan = (const char *)fwd_plan_dev;
+        FwdFewArgs k;
+        k.clist = reinterpret_cast<const int *>(plan + L.off_clist);
+        k.inv_ncls = reinterpret_cast<const unsigned *>(plan + L.off_clist + 2ll * (A + 1) * 4);
+        k.rng = reinterpret_cast<const int *>(plan + L.off_rng);
+        k.idx = reinterpret_cast<const uint4 *>(plan + L.off_idx);
+        k.A = A, k.A1 = A + 1, k.rows = H, k.cs = W == 64 ? 0 : (W == 128 ? 1 : 2), k.src_stride = W, k.pitch = L.pitch, k.zero = L.zero;
+        k.PW = PW, k.nJB = L.nJB, k.st = L.PWpad, k.ast = L.Galloc * L.PWpad;
+        k.G = sh.wgs_per_slice / 2, k.wgs = sh.wgs_per_slice, k.S = S, k.units = sh.units, k.slice = H * W;
+        k.inv_wgs = div_magic((unsigned)sh.wgs_per_slice);
+        auto launch_few = [&](auto kernel) -> int {
+            static std::atomic<unsigned long long> attr_set{0}, abs_ok{0};   // per kernel instantiation: devices done
+            CTPVAE_REQUIRE_NO_STATIC_LDS(kernel, "rotate_fwd_planned_kernel_few", abs_ok);
+            CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)sh.grid), dim3(64 * sh.waves), sh.shmem, (hipStream_t)stream, img_dev, sino_dev, k);
+            CTPVAE_LAUNCH_CHECK("rotate_fwd_planned_kernel_few");
+            return CTPVAE_OK;
+        };
+        return ns == 2 ? launch_few(rotate_fwd_planned_kernel_few<2>) : launch_few(rotate_fwd_planned_kernel_few<1>);
+    }
     auto launch = [&](auto kernel) -> int {
         static std::atomic<unsigned long long> attr_set{0}, abs_ok{0};   // per kernel instantiation: devices done
         CTPVAE_REQUIRE_NO_STATIC_LDS(kernel, "rotate_fwd_planned_kernel", abs_ok);
         CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
-        // divisions by multiplication (div_magic): piece numbers / 8 by the pieces per unit, task numbers by a class's angle count
-        const int small_div = (grid / 8 + 1) * (long long)std::max(wgs_per_slice, std::max(wgs2, wgs3)) < (1ll << 32) && (long long)A * L.nJB * A < (1ll << 32) &&
-                                      knob(kKnobNoMagic) <= 0 ? 1 : 0;
-        hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * waves), shmem, (hipStream_t)stream,
-                           img_dev, g, L, (const char *)fwd_plan_dev, wgs_per_slice, S, sino_dev, epi, sel_dev, n_sel, affine, units1, wgs2,
-                           div_magic((unsigned)wgs_per_slice), div_magic((unsigned)wgs2), small_div, units2, wgs3, div_magic((unsigned)wgs3));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)sh.grid), dim3(64 * sh.waves), sh.shmem, (hipStream_t)stream,
+                           img_dev, g, L, (const char *)fwd_plan_dev, sh.wgs_per_slice, S, sino_dev, epi, sel_dev, n_sel, sh.affine, sh.units1, sh.wgs2,
+                           div_magic((unsigned)sh.wgs_per_slice), div_magic((unsigned)sh.wgs2), sh.small_div, sh.units2, sh.wgs3, div_magic((unsigned)sh.wgs3));
         CTPVAE_LAUNCH_CHECK("rotate_fwd_planned_kernel");
         return CTPVAE_OK;
     };
@@ -1423,6 +1612,13 @@ static int launch_fwd_planned(const float *img_dev, int S, int H, int W, int PH,
     }
     if (epi.lp) return ns == 2 ? launch(rotate_fwd_planned_kernel<2, true, false>) : launch(rotate_fwd_planned_kernel<1, true, false>);
     return ns == 2 ? launch(rotate_fwd_planned_kernel<2, false, false>) : launch(rotate_fwd_planned_kernel<1, false, false>);
+}
+
+int ctpvae_rotate_fwd_planned_form(int S, int H, int W, int PH, int PW, int A, int img_aligned16)
+{
+    FwdShape sh;
+    if (int rc = fwd_planned_shape(S, H, W, PH, PW, A, false, 0, sh)) return rc;
+    return fwd_few_ok(sh, true, img_aligned16 != 0) ? 1 : 0;
 }
 
 int ctpvae_rotate_fwd_planned_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A, const void *fwd_plan_dev,

@@ -424,6 +424,16 @@ class RotatePlan:
             return "rotate_fwd_fast_kernel"
         return "rotate_fwd_compact_kernel" if self.dense_plan(S)[1] else "rotate_fwd_planned_kernel"
 
+    def forward_form(self, S, img=None):
+        """Which form of rotate_fwd_planned_kernel a dense forward() over S slices launches: 1 = the lean form for few-task launches
+        (rotate_fwd_planned_kernel_few), 0 = the general kernel (or another kernel altogether: see forward_kernel_name).  `img`: the
+        tensor that would be projected -- the lean form needs it 16-byte aligned; without it an aligned one is assumed."""
+        if self.forward_kernel_name(S) != "rotate_fwd_planned_kernel":
+            return 0
+        aligned = 1 if img is None or img.data_ptr() % 16 == 0 else 0
+        return _lib.check(self._lib.ctpvae_rotate_fwd_planned_form(S, self.H, self.W, self.PH, self.PW, self.A, aligned),
+                          "rotate_fwd_planned_form")
+
     def _run_compact(self, img_ptr, S, out_ptr, angles_i=None, n=0, mask=None, meas=None, dense=0, pnm=None, eps=0.0,
                      lp_ptr=None, dlp_ptr=None, part_ptr=None, sum_ptr=None, noise=0):
         if noise:    # the twin entry point with the noise model as an operand (0 = this one's, so the Gaussian call is unchanged)

@@ -236,6 +236,10 @@ int ctpvae_rotate_plan_build_f32(const float *T8_dev, const float *Tinv8_dev, in
                                  int py, int px, void *fwd_plan_dev, void *bwd_plan_dev, ctpvae_stream_t stream);
 int ctpvae_rotate_fwd_planned_f32(const float *img_dev, int S, int H, int W, int PH, int PW, int A,
                                   const void *fwd_plan_dev, float *sino_dev, ctpvae_stream_t stream);
+/* Host only (added at ABI 3400): which form of the kernel ctpvae_rotate_fwd_planned_f32 launches for this shape -- 1 = the lean form
+ * for few-task launches of one round of workgroups (rotate_fwd_planned_kernel_few), 0 = the general kernel; negative on bad sizes.
+ * Same bits either way.  img_aligned16: whether img_dev is 16-byte aligned.  Honours the developer knobs (FWD_FEW = 0: always 0). */
+int ctpvae_rotate_fwd_planned_form(int S, int H, int W, int PH, int PW, int A, int img_aligned16);
 /* a8 fused into a2: the planned forward that also writes, for every ray-sum, the log-probability of the
  * measured sample under it -- lp[s][a][j] = ctpvae_loglik_fwd_f32's expression on (sino[s][a][j], mask[s][a],
  * meas[s][a][j]) -- in the same launch.  sino_dev is still written.  dlp_dev (may be NULL) receives

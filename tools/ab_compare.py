@@ -4,6 +4,7 @@ cold first measurement reads ~15 % slow).
 
     CTPVAE_VARIANT_LIB=tools/libctpvae_radon_<tag>.bin python tools/ab_compare.py      (an older build: same C ABI)
     python tools/ab_compare.py                                                          (the in-tree library)
+    python tools/ab_compare.py quick                                                    (the one-round forwards alone)
 
 Each figure: HIP-graph replay of N launches between two events, after three untimed warm-up rounds."""
 import os
@@ -16,8 +17,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from ct_pvae_amd import _lib
 
 if os.environ.get("CTPVAE_VARIANT_LIB"):
+    import ctypes
     _lib.LIB_PATH = os.path.abspath(os.environ["CTPVAE_VARIANT_LIB"])
     _lib.torch_node = lambda: None      # the C++ autograd node binds the in-tree library: not used here
+    _old = ctypes.CDLL(_lib.LIB_PATH)   # (an older build of the same ABI may lack entry points added since: none is called here)
+    _lib.SIGNATURES = {k: v for k, v in _lib.SIGNATURES.items() if hasattr(_old, k)}
 from ct_pvae_amd import phantoms
 from ct_pvae_amd.forward_functions import RotatePlan
 
@@ -46,6 +50,15 @@ def timed(body, n):
 
 
 print("library:", _lib.LIB_PATH, flush=True)
+# one-round launches of the planned forward (few tasks per workgroup: mostly prologue)
+for B in (1, 5, 25, 50):
+    theta = phantoms.dense_theta(180)[:: 180 // 20]
+    plan = RotatePlan(theta, 128, 128, True, d)
+    x = torch.rand((B, 128, 128), device=d)
+    out = torch.empty((B, 20, plan.PW), device=d)
+    print(f"128x128 B={B} A=20 [{plan.forward_kernel_name(B)}]: fwd {timed(lambda: plan.forward(x, out=out), 200):.2f} us", flush=True)
+if "quick" in sys.argv[1:]:
+    sys.exit(0)
 for B, A in ((50, 20), (50, 180), (400, 20), (400, 180)):
     theta = phantoms.dense_theta(180)[:: 180 // A]
     plan = RotatePlan(theta, 128, 128, True, d)

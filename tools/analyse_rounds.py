@@ -88,6 +88,15 @@ def analyse(path):
     cols.append(("end", np.median((d[:, :, 6] - d[:, :, 3]) / cyc_per_us, axis=0)))
     for name, v in cols:
         print(f"   per wave, {name:15s} (us{'' if name == 'starts' else ' after its own start'}): " + " ".join(f"{x:5.2f}" for x in v))
+    # waves with and without a task, over all workgroups.  Told apart by TIME (a wave without a task ends right behind the barrier: under
+    # 0.2 us), not by wave number -- the stamps do not hold a workgroup's task count; a task wave whose range is empty (ng == 0: no ray of
+    # its bin block meets the slice) would be counted as task-less.  No such task exists at the shapes this is used on (128 x 128 padded).
+    staged = (d[:, :, 5] - d[:, :, 3]) / cyc_per_us
+    after = (d[:, :, 6] - d[:, :, 5]) / cyc_per_us
+    for name, m in (("task waves", after >= 0.2), ("task-less waves", after < 0.2)):
+        if m.any():
+            print(f"   {name:15s}: {int(m.sum()):5d} | start -> staged p50/p90 {np.median(staged[m]):5.2f} {np.percentile(staged[m], 90):5.2f}"
+                  f" | staged -> end p50/p90 {np.median(after[m]):5.2f} {np.percentile(after[m], 90):5.2f}")
     busy = sum(end[w] - start[w] for w in range(nwg))
     print(f"   CU occupancy: {busy / (256 * span) * 100:.1f} % of 256 CUs x span held by a workgroup; "
           f"staged-and-gathering (barrier -> longest wave's end): {sum(tasks_max) / (256 * span) * 100:.1f} %; "

@@ -1,11 +1,11 @@
-"""Developer tool (no GPU needed): the static prologue of the planned backward, per instantiation.
+"""Developer tool (no GPU needed): the static prologue of a planned kernel (default: the planned backward), per instantiation.
 
 Compiles ct_pvae_amd/csrc/rotate_plan.hip device-only to gfx950 assembly with the library's flags and prints, for every
-rotate_bwd_planned_kernel instantiation, the number of instructions ahead of its first s_barrier and how many of them belong to
+instantiation whose name holds the given kernel name (default rotate_bwd_planned_kernel), the number of instructions ahead of its first s_barrier and how many of them belong to
 integer-division expansions (v_rcp_iflag_f32: one per unsigned / signed 32-bit division; s_abs_i32: the sign handling of a signed
 one).  Static order is not the dynamic path, but a division by a launch constant that is still in the listing is still paid.
 
-    python tools/count_prologue_isa.py [more hipcc flags ...]
+    python tools/count_prologue_isa.py [kernel name, e.g. rotate_fwd_planned_kernel] [more hipcc flags ...]
 """
 import os
 import re
@@ -63,6 +63,8 @@ def count(asm, kernel=KERNEL):
 
 
 if __name__ == "__main__":
-    for name, r in sorted(count(assembly(sys.argv[1:])).items()):
+    argv = sys.argv[1:]
+    kernel = argv.pop(0) if argv and not argv[0].startswith("-") else KERNEL
+    for name, r in sorted(count(assembly(argv), kernel).items()):
         print("%-58s prologue %4d of %5d instructions, v_rcp_iflag_f32 %2d, s_abs_i32 %2d"
               % (name, r["prologue"], r["total"], r["v_rcp_iflag_f32"], r["s_abs_i32"]))
