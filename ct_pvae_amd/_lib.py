@@ -164,6 +164,10 @@ SIGNATURES = {
                                        ctypes.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_latent_draws_host_f32": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                               _vp]),
+    "ctpvae_periodic_pad_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "ctpvae_periodic_pad_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "ctpvae_maxout_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_maxout_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
 }
 
 _lib = None

@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from . import dataset_io, phantoms, sharding
+from .convblock import maxout, periodic_pad
 from .create_masks import create_all_masks
 from .fbp import iradon_all
 from .forward_functions import num_proj_pix
@@ -109,11 +110,13 @@ class _PeriodicPad(torch.autograd.Function):
 
 class ConvBlock(nn.Module):
     """Conv2D => maxout of two convolutions (ctvae/models.py:267-342); 'periodic' padding for the strided/plain
-    convolutions (:219-263), Conv2DTranspose(padding='same') for up-sampling."""
+    convolutions (:219-263), Conv2DTranspose(padding='same') for up-sampling.  fused_blocks: the padding and the maxout are one launch
+    each way (convblock.periodic_pad / maxout, csrc/convblock.hip) instead of _PeriodicPad's and _Maxout's chains of torch launches;
+    the parameters and their names are the same either way."""
 
-    def __init__(self, cin, cout, k, stride, transpose):
+    def __init__(self, cin, cout, k, stride, transpose, fused_blocks=False):
         super().__init__()
-        self.k, self.stride, self.transpose = k, stride, transpose
+        self.k, self.stride, self.transpose, self.fused_blocks = k, stride, transpose, bool(fused_blocks)
         # the two convolutions of the maxout are ONE convolution with 2 * cout output channels (half the launches);
         # each half is initialised as its own GlorotUniform layer
         if transpose:
@@ -137,22 +140,22 @@ class ConvBlock(nn.Module):
             for n in (x.shape[-1], x.shape[-2]):   # last axis first, as torch.nn.functional.pad orders them
                 p = self.k - (n % self.stride if n % self.stride else self.stride)
                 pads += [p // 2 + p % 2, p // 2]
-            x = _PeriodicPad.apply(x, tuple(pads))
-        return _Maxout.apply(self.ab(x))
+            x = periodic_pad(x.contiguous(), tuple(pads)) if self.fused_blocks else _PeriodicPad.apply(x, tuple(pads))
+        return maxout(self.ab(x).contiguous()) if self.fused_blocks else _Maxout.apply(self.ab(x))
 
 
 class EncodeNet(nn.Module):
     """create_encode_net, ctvae/models.py:23-108: returns the list of skips (the first one is the repeated input)."""
 
-    def __init__(self, cin, feature_maps, fmm, kernel, stride, inter_layers, inter_kernel):
+    def __init__(self, cin, feature_maps, fmm, kernel, stride, inter_layers, inter_kernel, fused_blocks=False):
         super().__init__()
         self.fmm = fmm
         c = cin * fmm
         self.channels = [c]
         self.blocks = nn.ModuleList()
         for f in feature_maps:
-            layers = [ConvBlock(c, c, inter_kernel, 1, False) for _ in range(inter_layers)]
-            layers.append(ConvBlock(c, f * fmm, kernel, stride, False))
+            layers = [ConvBlock(c, c, inter_kernel, 1, False, fused_blocks=fused_blocks) for _ in range(inter_layers)]
+            layers.append(ConvBlock(c, f * fmm, kernel, stride, False, fused_blocks=fused_blocks))
             self.blocks.append(nn.Sequential(*layers))
             c = f * fmm
             self.channels.append(c)
@@ -169,17 +172,18 @@ class EncodeNet(nn.Module):
 class DecodeNet(nn.Module):
     """create_decode_net, ctvae/models.py:112-215 (the code concatenates every skip, including the input level)."""
 
-    def __init__(self, enc_channels, fmm, out_channels, kernel, stride, inter_layers, inter_kernel):
+    def __init__(self, enc_channels, fmm, out_channels, kernel, stride, inter_layers, inter_kernel, fused_blocks=False):
         super().__init__()
         lat = [c // fmm for c in enc_channels]     # channels of the sampled latents
         self.ups = nn.ModuleList()
         c = lat[-1]
         for lvl in range(len(enc_channels) - 2, -1, -1):
-            layers = [ConvBlock(c, enc_channels[lvl], kernel, stride, True)]
-            layers += [ConvBlock(enc_channels[lvl], enc_channels[lvl], inter_kernel, 1, False) for _ in range(inter_layers)]
+            layers = [ConvBlock(c, enc_channels[lvl], kernel, stride, True, fused_blocks=fused_blocks)]
+            layers += [ConvBlock(enc_channels[lvl], enc_channels[lvl], inter_kernel, 1, False, fused_blocks=fused_blocks)
+                       for _ in range(inter_layers)]
             self.ups.append(nn.Sequential(*layers))
             c = enc_channels[lvl] + lat[lvl]
-        self.head = ConvBlock(c, 2 * out_channels, kernel, 1, False)
+        self.head = ConvBlock(c, 2 * out_channels, kernel, 1, False, fused_blocks=fused_blocks)
 
     def forward(self, latents):
         x = latents[-1]
@@ -358,8 +362,9 @@ class PVAETrainer:
         self._make_data()
         fm = [int(a.nfm * a.nfmm ** i) for i in range(a.num_blocks)]
         fmm = 1 if a.deterministic else 2
-        self.enc = EncodeNet(len(a.algorithms) + 1, fm, fmm, a.kernel_size, a.stride_encode, a.il, a.ik).to(device)
-        self.dec = DecodeNet(self.enc.channels, fmm, 1, a.kernel_size, a.stride_encode, a.il, a.ik).to(device)
+        fused_blocks = bool(getattr(a, "fused_blocks", False))
+        self.enc = EncodeNet(len(a.algorithms) + 1, fm, fmm, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks).to(device)
+        self.dec = DecodeNet(self.enc.channels, fmm, 1, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks).to(device)
         if self.world > 1:   # identical initial weights on every rank
             for p in list(self.enc.parameters()) + list(self.dec.parameters()):
                 torch.distributed.broadcast(p.data, 0)
@@ -642,6 +647,12 @@ def get_args(argv=None):
                    help="sample the Normal latents and sum their KL term in one launch per skip level (csrc/latent.hip), with Philox "
                         "draws keyed by (--head_seed, step index, level, sample, global object) instead of torch's global generator; "
                         "needs --normal, not with --det")
+    p.add_argument("--fused_blocks", action="store_true",
+                   help="the periodic pad in front of every ConvBlock's convolution and the maxout behind it as one launch each way "
+                        "(csrc/convblock.hip) instead of chains of small torch launches; the same parameters, checkpoints and, with at most "
+                        "two copies of a pixel per axis, the same values; independent of --normal and --det.  Measured at the c3 recipe "
+                        "(profiles/convblock_timing.txt): alone NOT measurably faster (173.8 against 173.1 steps/s, the windows overlap); "
+                        "with --fused_head --fused_latents 248.1 against 237.6 steps/s, the windows overlap too")
     p.add_argument("--reproducible", action="store_true",
                    help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
                         "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")

@@ -722,6 +722,24 @@ int ctpvae_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, float s
 int ctpvae_latent_draws_host_f32(int n, int len, int ns, long long first_object, unsigned long long seed, unsigned draw, unsigned level,
                                  float *v_out_host);
 
+/* ---- the glue around every convolution of the P-VAE's ConvBlock (ctvae/models.py:219-263, :330-341) as one launch each way
+ * (csrc/convblock.hip states the functions and the backward's order of addition).  All tensors fp32, contiguous [N][C][H][W].
+ * Periodic pad, planes = N * C, OH = H + hl + hr, OW = W + wl + wr (a pad may exceed the extent):
+ *   _pad_fwd_f32: out_dev [planes][OH][OW], out[p][r][q] = x[p][(r - hl) mod H][(q - wl) mod W].
+ *   _pad_bwd_f32: gx_out_dev [planes][H][W] for the cotangent g_dev [planes][OH][OW]: per padded row the copies of a column added in
+ *     ascending q, then the rows of a source row in ascending r, each sum starting from its first term; no atomics.
+ * Maxout, y_dev [n][2][len] (len = C * H * W; the two channel halves of an object):
+ *   _maxout_fwd_f32: first = y[n][0][i] >= y[n][1][i] (a tie takes the first half, a NaN in either the second);
+ *     out_dev [n][len] = first ? first half : second half, first_out_dev [n][len] one byte per element (0 or 1), all the backward needs.
+ *   _maxout_bwd_f32: gy_out_dev [n][2][len] = (first ? g : 0, first ? 0 : g) for the cotangent g_dev [n][len]; every element is written.
+ * Every extent >= 1, every pad >= 0, every element count (planes * OH * OW, 2 * n * len) <= 2^31 - 1. */
+int ctpvae_periodic_pad_fwd_f32(const float *x_dev, int planes, int H, int W, int wl, int wr, int hl, int hr, float *out_dev,
+                                ctpvae_stream_t stream);
+int ctpvae_periodic_pad_bwd_f32(const float *g_dev, int planes, int H, int W, int wl, int wr, int hl, int hr, float *gx_out_dev,
+                                ctpvae_stream_t stream);
+int ctpvae_maxout_fwd_f32(const float *y_dev, int n, int len, float *out_dev, unsigned char *first_out_dev, ctpvae_stream_t stream);
+int ctpvae_maxout_bwd_f32(const float *g_dev, const unsigned char *first_dev, int n, int len, float *gy_out_dev, ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
