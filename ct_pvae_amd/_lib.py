@@ -12,6 +12,7 @@ LIB_PATH = os.path.join(_HERE, "libctpvae_radon.so")
 NEAREST, BILINEAR = 0, 1
 NOISE = {"gaussian": 0, "poisson": 1}     # CTPVAE_NOISE_*
 BWD_TF_COMPAT, BWD_EXACT = 0, 1
+SIDDON_STORE = {"raysum": 0, "sirt": 1, "tv_dual": 2, "gaussian": 3, "poisson": 4, "ratio": 5}     # CTPVAE_SIDDON_STORE_*
 EINVAL, EHIP, ENODEV = -1, -2, -3
 ABI_VERSION = 3400   # ctpvae_abi_version() of the library this binding was written for
 
@@ -132,6 +133,7 @@ SIGNATURES = {
                                              _vp]),
     "ctpvae_siddon_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp, _vp]),
     "ctpvae_siddon_rownorm_f32": (_c_int, [_c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_float, _vp, _vp]),
+    "ctpvae_siddon_fwd_form": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int]),
     "ctpvae_fbp_filter_f64": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "ctpvae_fbp_backproject_f64": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _vp, _vp]),
     "ctpvae_fbp_backproject_bwd_f64": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int, ctypes.c_double,

@@ -1049,12 +1049,13 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
                           const float *rn2_dev, int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr,
                           int noise = 0);
 static float siddon_mov(int dx, float center);
+static int siddon_fwd_chunk_slices();
 
 static int siddon_fwd_chunks(const float *obj_dev, int oy, int ox, int oz, const float *sin_dev, const float *cos_dev,
                              const int *quad_dev, int dt, int dx, float center, const float *meas_dev, const float *rn2_dev,
                              int mode, float *data_dev, ctpvae_stream_t stream, const SidLogLik *ll = nullptr, int noise = 0)
 {
-    const int chunk = std::max(2, max_slices_per_launch() / 2 * 2);   // even: whole slice pairs per chunk
+    const int chunk = siddon_fwd_chunk_slices();
     for (int s0 = 0; s0 < oy; s0 += chunk) {
         const int n = std::min(chunk, oy - s0);
         SidLogLik lls{};
@@ -1076,19 +1077,56 @@ int ctpvae_siddon_fwd_f32(const float *obj_dev, int oy, int ox, int oz, const fl
     return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, nullptr, nullptr, 0, data_dev, stream);
 }
 
-// slices per walk of the packed forward: 0 = keep the LDS kernels (few slices, or a grid whose PAIRS fit LDS and ... see below)
-static int siddon_packed_ns(int oy, int ox, int oz)
+// THE dispatch rule of the forward: which form a launch of `oy` slices takes -- 0 = one slice per workgroup read from global memory (a
+// slice does not fit LDS), 1 = one slice in LDS, 2 = a slice pair in LDS, 4 / 8 = the packed walk with that many slices behind a
+// ray.  Every launch (siddon_fwd_ws, siddon_fwd_one), the workspace's size rule and the host-only query ctpvae_siddon_fwd_form ask
+// this one function, so they cannot drift apart.  lds_only: the caller has no workspace (ctpvae_siddon_fwd_f32 / _resid, and the
+// chunks of a call that did not take the packed walk); poisson: the Poisson likelihood store, which has no packed form.
+static int siddon_fwd_form_rule(int oy, int ox, int oz, long long dt, long long dx, bool poisson, bool lds_only)
 {
-    if (knob(kKnobSiddonNs) == 1 || knob(kKnobSiddonNs) == 2) return 0;       // the knob asks for an LDS kernel
-    if (knob(kKnobSiddonNs) == 4 || knob(kKnobSiddonNs) == 8) return knob(kKnobSiddonNs);
-    return oy >= 6 ? 8 : oy >= 3 ? 4 : 0;
+    const int kn = knob(kKnobSiddonNs);
+    const size_t lds_one = (size_t)ox * (oz + ((1 - (oz & 31)) & 31)) * sizeof(float);
+    const bool pair_fits = 2 * lds_one <= (size_t)kMaxLdsBytes;
+    if (!lds_only) {
+        // slices per walk of the packed forward: 0 = keep the LDS kernels (few slices, or the knob asks for an LDS kernel)
+        int ns = (kn == 4 || kn == 8) ? kn : (kn == 1 || kn == 2) ? 0 : oy >= 6 ? 8 : oy >= 3 ? 4 : 0;
+        // A launch of few waves takes as long as ONE walk -- 55-70 us with eight slices behind a ray (packed, objects through the L2),
+        // 43-47 us with the slice pair in LDS: up to ~750 waves of pairs the LDS kernels are the faster ones (16 x 128^2 x 20 angles:
+        // 47.4 against 67.6 us, 24 x 20: 47.4 against 67.6; 32 x 20, 920 waves of pairs: 75.6 against 66-69; tools/sweep_siddon_ns.py)
+        if (ns != 0 && kn < 0 && pair_fits && (long long)ceil_div(oy, 2) * dt * dx <= 750ll * 64) ns = 0;
+        // noise = poisson: the likelihood store has its poisson form in the LDS / global-memory kernels only (the same walk and order
+        // of the sum: the same ray-sums; large batches give up the packed walk, 66-69 against 75.6 us at 32 x 20 in the sweep above;
+        // the Poisson call itself has not been timed)
+        if (poisson) ns = 0;
+        if (ns != 0) return ns;
+    }
+    if (lds_one > (size_t)kMaxLdsBytes) return 0;
+    // two slices per workgroup when the pair fits LDS and the call has slices to pair
+    // (... and up to ~500 waves single slices: more workgroups of the same walk -- 8 x 128^2 x 20 angles 43.8 us single, 47.1 paired)
+    int ns = (oy >= 2 && pair_fits && (long long)oy * dt * dx > 500ll * 64) ? 2 : 1;
+    if (kn >= 0) ns = (kn == 2 && oy >= 2 && pair_fits) ? 2 : 1;
+    return ns;
 }
+// slices of one launch of the LDS / global-memory kernels: even, so whole slice pairs per chunk
+static int siddon_fwd_chunk_slices() { return std::max(2, max_slices_per_launch() / 2 * 2); }
 
+// (the size rule knows neither the angles nor the detector: it answers for a launch too large to keep the LDS kernels, so a
+// workspace of this size serves every call on these slices)
 long long ctpvae_siddon_fwd_workspace_bytes(int oy, int ox, int oz)
 {
     if (oy <= 0 || ox <= 0 || oz <= 0) return fail(CTPVAE_EINVAL, "siddon_fwd_workspace_bytes: bad sizes");
-    const int ns = siddon_packed_ns(oy, ox, oz);
-    return ns ? (long long)ceil_div(oy, ns) * ns * ox * oz * (long long)sizeof(float) : 0;
+    const int form = siddon_fwd_form_rule(oy, ox, oz, 1 << 15, 1 << 15, false, false);
+    return form >= 4 ? (long long)ceil_div(oy, form) * form * ox * oz * (long long)sizeof(float) : 0;
+}
+
+int ctpvae_siddon_fwd_form(int oy, int ox, int oz, int dt, int dx, int store)
+{
+    CTPVAE_REQUIRE(oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0, "siddon_fwd_form: sizes must be positive (oy=%d ox=%d oz=%d dt=%d dx=%d)",
+                   oy, ox, oz, dt, dx);
+    CTPVAE_REQUIRE(store >= CTPVAE_SIDDON_STORE_RAYSUM && store <= CTPVAE_SIDDON_STORE_RATIO, "siddon_fwd_form: unknown store %d", store);
+    const int form = siddon_fwd_form_rule(oy, ox, oz, dt, dx, store == CTPVAE_SIDDON_STORE_POISSON, false);
+    if (form >= 4) return form;
+    return siddon_fwd_form_rule(std::min(oy, siddon_fwd_chunk_slices()), ox, oz, dt, dx, false, true);   // the first chunk's launch
 }
 
 }  // extern "C"
@@ -1125,17 +1163,8 @@ static int siddon_fwd_ws(const float *obj_dev, int oy, int ox, int oz, const flo
     CTPVAE_REQUIRE(obj_dev && (data_dev || ll) && sin_dev && cos_dev && quad_dev && oy > 0 && ox > 0 && oz > 0 && dt > 0 && dx > 0,
                    "siddon_fwd: null pointer or empty sizes");
     CTPVAE_REQUIRE((meas_dev == nullptr) == (rn2_dev == nullptr), "siddon_fwd: meas and the per-ray weights go together");
-    int ns = siddon_packed_ns(oy, ox, oz);
-    // A launch of few waves takes as long as ONE walk -- 55-70 us with eight slices behind a ray (packed, objects through the L2),
-    // 43-47 us with the slice pair in LDS: up to ~750 waves of pairs the LDS kernels are the faster ones (16 x 128^2 x 20 angles: 47.4
-    // against 67.6 us, 24 x 20: 47.4 against 67.6; 32 x 20, 920 waves of pairs: 75.6 against 66-69; tools/sweep_siddon_ns.py)
-    if (ns != 0 && knob(kKnobSiddonNs) < 0 && 2 * (size_t)ox * (oz + ((1 - (oz & 31)) & 31)) * sizeof(float) <= (size_t)kMaxLdsBytes &&
-        (long long)ceil_div(oy, 2) * dt * dx <= 750ll * 64)
-        ns = 0;
-    // noise = poisson: the likelihood store has its poisson form in the LDS / global-memory kernels only (the same walk and order
-    // of the sum: the same ray-sums; large batches give up the packed walk, 66-69 against 75.6 us at 32 x 20 in the sweep above;
-    // the Poisson call itself has not been timed)
-    if (ll && noise == CTPVAE_NOISE_POISSON) ns = 0;
+    int ns = siddon_fwd_form_rule(oy, ox, oz, dt, dx, ll && noise == CTPVAE_NOISE_POISSON, false);
+    if (ns < 4) ns = 0;      // an LDS / global-memory form: decided per chunk in siddon_fwd_one
     if (ns == 0)
         return siddon_fwd_chunks(obj_dev, oy, ox, oz, sin_dev, cos_dev, quad_dev, dt, dx, center, meas_dev, rn2_dev, mode, data_dev, stream, ll, noise);
     CTPVAE_REQUIRE(workspace_dev, "siddon_fwd: %d slices need the workspace", oy);
@@ -1184,11 +1213,9 @@ static int siddon_fwd_one(const float *obj_dev, int oy, int ox, int oz, const fl
     CTPVAE_REQUIRE(oy <= 65535, "siddon_fwd: at most 65535 slices per call (got %d)", oy);
     const SidGeom g{oy, ox, oz, dt, dx, siddon_mov(dx, center)};
     const size_t lds_one = (size_t)ox * (oz + ((1 - (oz & 31)) & 31)) * sizeof(float);
-    const bool use_lds = lds_one <= (size_t)kMaxLdsBytes;
-    // two slices per workgroup when the pair fits LDS and the call has slices to pair
-    // (... and up to ~500 waves single slices: more workgroups of the same walk -- 8 x 128^2 x 20 angles 43.8 us single, 47.1 paired)
-    int ns = (oy >= 2 && 2 * lds_one <= (size_t)kMaxLdsBytes && (long long)oy * dt * dx > 500ll * 64) ? 2 : 1;
-    if (knob(kKnobSiddonNs) >= 0) ns = (knob(kKnobSiddonNs) == 2 && oy >= 2 && 2 * lds_one <= (size_t)kMaxLdsBytes) ? 2 : 1;
+    const int form = siddon_fwd_form_rule(oy, ox, oz, dt, dx, false, true);      // 0, 1 or 2
+    const bool use_lds = form != 0;
+    const int ns = form == 2 ? 2 : 1;
     const int units = ceil_div(oy, ns);
     const size_t lds_bytes = lds_one * ns;
     int ppb = dt;

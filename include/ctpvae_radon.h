@@ -72,7 +72,10 @@ typedef void *ctpvae_stream_t;
 
 /* Version of this ABI: major * 1000 + minor.  CTPVAE_ABI_VERSION is what THIS header describes: host code compiled against
  * it (csrc/torch_node.cpp, a maintainer's own binding) compares the macro with ctpvae_abi_version() of the library it loaded
- * and refuses a mismatch -- an entry point called with another version's argument list is a silent wrong-argument call. */
+ * and refuses a mismatch -- an entry point called with another version's argument list is a silent wrong-argument call.
+ * The rule: the version changes when an EXISTING entry point changes its argument list or what it computes; an ADDED entry point
+ * keeps it ("added at ABI 3400" below).  A binding that needs an added symbol therefore also checks that the library has it
+ * (ct_pvae_amd/_lib.py resolves every name when it loads: a library without one fails there, not in a call). */
 #define CTPVAE_ABI_VERSION 3400
 int ctpvae_abi_version(void);
 /* Thread-local message of the last failing call on this thread ("" if none). */
@@ -429,6 +432,22 @@ int ctpvae_siddon_fwd_ws_f32(const float *obj_dev, int oy, int ox, int oz, const
                              void *workspace_dev, float *data_dev, ctpvae_stream_t stream);
 int ctpvae_siddon_rownorm_f32(int ox, int oz, const float *sin_dev, const float *cos_dev, const int *quad_dev, int dt,
                               int dx, float center, float *rn2_dev, ctpvae_stream_t stream);
+/* Host only (added at ABI 3400): which form of the forward kernel a call of the entry points that take a workspace
+ * (ctpvae_siddon_fwd_ws_f32, _fwd_ws_tv_dual, _fwd_loglik, _fwd_loglik_noise, _fwd_ratio) launches for these sizes and the current
+ * developer knobs -- 0 = one slice per workgroup read from global memory (a slice does not fit LDS), 1 = one slice in LDS, 2 = a
+ * slice pair in LDS, 4 / 8 = the packed walk with that many slices behind a ray (the workspace); negative on bad sizes or an
+ * unknown store.  dt: the rows the launch writes (n_sel with an angle subset).  store: CTPVAE_SIDDON_STORE_*; only _POISSON changes
+ * the answer (it has no packed form: never 4 or 8).  A batch longer than a launch takes (knob MAX_SLICES) goes in chunks: the
+ * answer is the first chunk's form (a shorter last chunk decides for its own size).  Same bits in every form.  The launches and
+ * ctpvae_siddon_fwd_workspace_bytes ask the same function (csrc/siddon.hip siddon_fwd_form_rule): the size rule is non-zero
+ * whenever the answer here is 4 or 8. */
+#define CTPVAE_SIDDON_STORE_RAYSUM 0   /* ctpvae_siddon_fwd_ws_f32 without meas */
+#define CTPVAE_SIDDON_STORE_SIRT 1     /* ctpvae_siddon_fwd_ws_f32 with meas / rn2: (meas - A x) / rn2 */
+#define CTPVAE_SIDDON_STORE_TV_DUAL 2  /* ctpvae_siddon_fwd_ws_tv_dual_f32 */
+#define CTPVAE_SIDDON_STORE_GAUSSIAN 3 /* ctpvae_siddon_fwd_loglik_f32, _noise with CTPVAE_NOISE_GAUSSIAN */
+#define CTPVAE_SIDDON_STORE_POISSON 4  /* ctpvae_siddon_fwd_loglik_noise_f32 with CTPVAE_NOISE_POISSON */
+#define CTPVAE_SIDDON_STORE_RATIO 5    /* ctpvae_siddon_fwd_ratio_f32 */
+int ctpvae_siddon_fwd_form(int oy, int ox, int oz, int dt, int dx, int store);
 /* The likelihood training call on the ray-driven projector (calculate_log_prob_M_given_R(model="siddon"),
  * ctvae/helper_functions.py:336-368), for the forward model the reference's data were made with.
  *   _fwd_loglik:  the forward of ctpvae_siddon_fwd_ws_f32 (same dispatch, same workspace rule, same ray-sums) whose store is the

@@ -77,6 +77,8 @@ def test_host_only_entry_points(built_lib):
     assert lib.ctpvae_pad_amounts(128, 184, ctypes.byref(lo), ctypes.byref(hi)) == 0
     assert (lo.value, hi.value) == (28, 28)
     assert lib.ctpvae_siddon_dx(128, 128, 1) == 184 and lib.ctpvae_siddon_dx(128, 128, 0) == 128
+    # the ray-driven forward's form query (its rule: tests/test_siddon_form_cpu.py): 5 slices of 184 x 184 take the packed walk of 4
+    assert lib.ctpvae_siddon_fwd_form(5, 184, 184, 20, 262, 0) == 4 and lib.ctpvae_siddon_fwd_form(1, 184, 184, 20, 262, 0) == 1
 
 
 def test_tiled_workspace_rule(built_lib):

@@ -118,7 +118,7 @@ def test_mlem_and_osem_match_the_twin(foam):
 
 
 @pytest.mark.parametrize("oy,n", [(2, 64), (5, 256)])
-def test_ratio_store_alone(oy, n):
+def test_ratio_store_alone(oracle, oy, n):
     """ctpvae_siddon_fwd_ratio_f32 with sel = NULL against data / ctpvae_siddon_fwd_ws_f32(x), element for element: 2 slices take the
     LDS kernels, 5 slices of 256^2 (a pair does not fit LDS) the packed walk with its workspace.  The detector is the padded one,
     wider than the grid: rays that miss the grid have a ray-sum of 0 and must give exactly 0."""
@@ -131,6 +131,8 @@ def test_ratio_store_alone(oy, n):
     x[0, : n // 2] = 0.0                                       # rays that cross pixels and still sum to 0
     meas = torch.from_numpy(rng.random((oy, 24, dx), dtype=np.float32) * 50.0).to(d)
     sim = to_np(_siddon_forward(x, tables, dx))
+    # ... and those ray-sums are the CPU oracle's, element for element: neither side of the comparison below rests on the GPU alone
+    np.testing.assert_array_equal(sim, np.swapaxes(oracle.siddon_project(to_np(x), theta, pad=True), 0, 1))
     got, used_workspace = fwd_ratio(x, tables, dx, meas)
     assert used_workspace == (oy >= 3)
     with np.errstate(all="ignore"):
