@@ -45,6 +45,34 @@ struct SliceScale {
     __device__ __forceinline__ float at(int s) const { return ptr ? ptr[(long long)s * stride] : 1.0f; }
 };
 
+// How a kernel stores its OUTPUT (a compile-time constant of the kernels that have the choice; knob WT_STORES).
+// A launch ends with a release that writes every XCD's dirty L2 lines back before a dependent launch may start; a write-through
+// store sends its line out while the kernel still runs and leaves nothing dirty behind.
+//   plain          global_store_*          the line stays dirty in the XCD's L2 until the end of the kernel
+//   write-through  global_store_* sc1      a relaxed agent-scope atomic store: through the L2 to memory, the line is dropped
+//   non-temporal   global_store_* nt       kept in L2 as a streaming line
+// One store instruction each and nothing else (tests/test_wt_stores_isa_cpu.py); the value stored is the same bits.
+// (value first, address second, as in `*p = v`: the compiler evaluates them in that order, and a plain helper call then compiles to the
+// very instructions of the assignment it replaces)
+enum StorePolicy { kStorePlain = 0, kStoreWriteThrough = 1, kStoreNonTemporal = 2 };
+template <int ST> __device__ __forceinline__ void store_f32(float v, float *p)
+{
+    if constexpr (ST == kStoreWriteThrough) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (ST == kStoreNonTemporal) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+// two consecutive floats, 8-byte aligned
+template <int ST> __device__ __forceinline__ void store_f32x2(float v0, float v1, float *p)
+{
+    typedef float f2_t __attribute__((ext_vector_type(2)));
+    const f2_t v = {v0, v1};
+    if constexpr (ST == kStoreWriteThrough)
+        __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (ST == kStoreNonTemporal) __builtin_nontemporal_store(v, reinterpret_cast<f2_t *>(p));
+    else *reinterpret_cast<f2_t *>(p) = v;
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of a kernel ON A DEVICE: it is set once per (kernel
 // instantiation, device) -- `seen` is that instantiation's bit mask of devices already done.  The bit is published only
 // AFTER the attribute call succeeded: a second thread that races the first simply sets the attribute again (harmless),
@@ -93,9 +121,17 @@ struct SliceScale {
 enum Knob {
     kKnobNoPlan, kKnobForceGeneric, kKnobNs, kKnobG, kKnobWaves, kKnobBns, kKnobBw, kKnobSegNs, kKnobSegChunk,
     kKnobSegPpt, kKnobTiledNs, kKnobTiledG, kKnobSiddonNs, kKnobSiddonThreads, kKnobSiddonPpb, kKnobMaxSlices,
-    kKnobSiddonBwdNs, kKnobSiddonBwdChunks, kKnobNoCompact, kKnobSkew0, kKnobTiledSort, kKnobTiledPair, kKnobAffine, kKnobFakeStaticLds, kKnobFoldSums, kKnobTiledXcd, kKnobTiledWaves, kKnobTiledTh, kKnobReduceWaves, kKnobStepNs, kKnobStepLdsKb, kKnobTiledForce, kKnobBsort, kKnobMixG, kKnobMixG2, kKnobMixU1, kKnobNoMagic, kKnobMixG1, kKnobMixG3, kKnobMixU2, kKnobBrsplit, kKnobFwdFew, kKnobCount
+    kKnobSiddonBwdNs, kKnobSiddonBwdChunks, kKnobNoCompact, kKnobSkew0, kKnobTiledSort, kKnobTiledPair, kKnobAffine, kKnobFakeStaticLds, kKnobFoldSums, kKnobTiledXcd, kKnobTiledWaves, kKnobTiledTh, kKnobReduceWaves, kKnobStepNs, kKnobStepLdsKb, kKnobTiledForce, kKnobBsort, kKnobMixG, kKnobMixG2, kKnobMixU1, kKnobNoMagic, kKnobMixG1, kKnobMixG3, kKnobMixU2, kKnobBrsplit, kKnobFwdFew, kKnobWtStores, kKnobCount
 };
 int knob(Knob k);
+
+// Knob WT_STORES: 0 = plain stores everywhere, 1 = write-through and 2 = non-temporal wherever a kernel has that form (a launch
+// without it runs its plain kernel), unset (or any other value) = the launch's own rule, `rule`.
+inline int store_policy(int rule)
+{
+    const int v = knob(kKnobWtStores);
+    return v >= 0 && v <= 2 ? v : rule;
+}
 
 // Kernels that index slices with a grid y / z dimension take at most this many per launch; their entry points split
 // longer batches (knob MAX_SLICES: a smaller limit, for the tests of that splitting).

@@ -852,257 +852,18 @@ __device__ __forceinline__ void gather8(const float *lds, unsigned w0, unsigned 
 // div_magic_floor words: no division behind them, knob NO_MAGIC does not apply), the wave number is a scalar, and the cotangent rows go
 // through stage_contig_rows (stage_magic != 0: the host found PW % 4 == 0 and a 16-byte aligned tensor) with the dead taps' zero cells
 // written while the loads fly; otherwise through the general stagers.
-template <int PPT, int MAXT, int NS, int DUP = 1, bool SHORT = false>
-__global__ __launch_bounds__(MAXT) void rotate_bwd_planned_kernel(const float *__restrict__ gsino, PlanGeom g, BwdLayout L,
-                                                                 const uint4 *__restrict__ idx, int tiles_y, int g_S,
-                                                                 SliceScale scale, float *__restrict__ gimg, unsigned inv_tiles,
-                                                                 unsigned inv_nxb, unsigned stage_magic)
-{
-    static_assert(!SHORT || DUP == 1, "SHORT launches are tf_compat plans of at most 32 angles");
-    typedef typename SliceVec<NS>::type vec_t;
-    constexpr int kChunk = kBwdChunk / NS;
-    extern __shared__ float lds[];
-    const int lane = threadIdx.x & 63, nwaves = blockDim.x >> 6;
-    const int wave = SHORT ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : threadIdx.x >> 6;
-    const int tiles = L.nXB * tiles_y;
-    const int units = (g_S + NS - 1) / NS;
-    // Workgroups b and b + 8 share an XCD (round-robin dispatch; speed only): the tiles of one slice (pair) are placed
-    // on one XCD so that its cotangent rows are fetched into one L2 -- block = (u / 8) * 8 * tiles + tile * 8 + u % 8.
-    int u, tile;
-    if constexpr (SHORT) {
-        const unsigned per8 = 8u * tiles, octet = div_by_magic_floor(blockIdx.x >> 3, inv_tiles, tiles), rem = blockIdx.x - octet * per8;
-        if ((int)(octet + 1) * 8 <= units) {
-            tile = rem >> 3;
-            u = octet * 8 + (rem & 7);
-        } else {
-            const unsigned ru = div_by_magic_floor(rem, inv_tiles, tiles);
-            u = octet * 8 + ru;
-            tile = rem - ru * tiles;
-        }
-    } else {
-        // (divisions by multiplication, div_magic: inv_tiles == 0 -- the host's "operands too large" -- divides)
-        const int per8 = 8 * tiles;
-        const int octet = inv_tiles ? (int)div_by_magic(blockIdx.x >> 3, inv_tiles) : (int)blockIdx.x / per8, rem = blockIdx.x - octet * per8;
-        if ((octet + 1) * 8 <= units) {
-            tile = rem >> 3;
-            u = octet * 8 + (rem & 7);
-        } else {   // the last, partial octet is laid out unit-major
-            const int ru = inv_tiles ? (int)div_by_magic((unsigned)rem, inv_tiles) : rem / tiles;
-            u = octet * 8 + ru;
-            tile = rem - ru * tiles;
-        }
-    }
-    const int s = u * NS;
-    const bool has2 = NS == 2 && s + 1 < g_S;   // an odd batch ends with a half-empty pair (slice s staged twice)
-    CTPVAE_PSTAMP(0);
-    // (the per-slice factors are wanted at the very end: a SHORT launch asks for them behind its barrier)
-    float k0 = 1.0f, k1 = 1.0f;
-    if constexpr (!SHORT) k0 = scale.at(s), k1 = has2 ? scale.at(s + 1) : 1.0f;
-    const int ty = SHORT ? (int)div_by_magic_floor((unsigned)tile, inv_nxb, (unsigned)L.nXB)
-                         : (inv_tiles ? (int)div_by_magic((unsigned)tile, inv_nxb) : tile / L.nXB),
-              xb = tile - ty * L.nXB;
-    // (SHORT: at most 32 x 255 cotangents per slice, and a plan of two index groups: 2 H Wpad < 2^32 vectors with check_plan_geom's
-    // PH PW < 2^24 -- unsigned 32-bit products)
-    const size_t slice_elems = SHORT ? (size_t)(unsigned)(g.A * g.PW) : (size_t)g.A * g.PW;
-    const float *gs = SHORT ? gsino + (size_t)s * slice_elems : gsino + (size_t)s * g.A * g.PW;
-    const int xcol = xb * 64 + lane;
-    const int y0 = ty * (nwaves * PPT) + wave;   // this wave's rows: y0, y0 + nwaves, ...
-    vec_t acc[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) acc[k] = 0.0f;
-    const uint4 *p = idx + (size_t)xcol;
-    // Index vectors of TWO groups of sixteen angles in flight (round 4; SHORT launches hold both of theirs anyway): with one,
-    // every wave of a many-angle launch waited out an L2 round trip per group -- SQ_WAIT_ANY was 46 % of the wave cycles at
-    // B = 50 x 180 angles with the LDS array 22 % busy -- and all sixteen waves of the CU's one workgroup did so together.
-    uint4 q[2][PPT];
-    auto load_group = [&](int a16, auto slot_tag) {
-        constexpr int SLOT = decltype(slot_tag)::value;
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int y = min(y0 + k * nwaves, g.H - 1);   // rows past the slice re-read the last row, never stored
-#ifdef CTPVAE_TUNE_BWD_NOIDX
-            if (a16 > 0) continue;   // timing only: every group reuses the first index vectors (no index streaming)
-#endif
-            q[SLOT][k] = SHORT ? p[(unsigned)(a16 * g.H + y) * (unsigned)L.Wpad] : p[((size_t)a16 * g.H + y) * L.Wpad];
-        }
-    };
-    load_group(0, std::integral_constant<int, 0>{});       // index loads fly while the cotangent rows land
-    if constexpr (!SHORT) load_group(min(1, L.NA16 - 1), std::integral_constant<int, 1>{});
-    [[maybe_unused]] uint4 q2nd[PPT];
-    if constexpr (SHORT) {
-#pragma unroll
-        for (int k = 0; k < PPT; ++k)
-            q2nd[k] = p[(unsigned)(min(1, L.NA16 - 1) * g.H + min(y0 + k * nwaves, g.H - 1)) * (unsigned)L.Wpad];   // (its second group)
-    }
-
-    const int VA = g.A * DUP;                            // virtual angles (= angles unless DUP = 2)
-    const int chunk = min(L.NA16 * 16, kChunk * DUP);    // virtual angles per staged chunk (a multiple of 16)
-    // Pairs in 16-wave workgroups (many angles, several chunks): the cotangent rows of chunk c + 1 are requested into
-    // registers (two units per lane) before the gathers of chunk c and written to LDS after them -- each chunk's load
-    // round trip hides behind the previous chunk's gather phase instead of standing between two barriers.
-    constexpr bool kPipe = NS == 2 && !SHORT;       // (the single-slice form has no registers to spare: 143 VGPRs with it)
-    constexpr int kAheadUnits = 2;                  // 32 rows of a pair over 16 waves
-    StagedRows<NS, kPipe ? kAheadUnits : 1> ahead;
-    bool ahead_valid = false;
-    auto chunk_srcs = [&](int ac, const float *(&srcs)[NS]) {
-        srcs[0] = gs + (size_t)ac * g.PW;
-        if constexpr (NS == 2) srcs[1] = gs + (has2 ? slice_elems : 0) + (size_t)ac * g.PW;
-    };
-    // (SHORT: the loop is its one trip with acv = 0 -- written so that the compiler sees it)
-    for (int acv = 0; acv < (SHORT ? 1 : VA); acv += (SHORT ? 1 : chunk)) {
-        const int nav = SHORT ? VA : min(chunk, VA - acv);
-        const int na4 = (nav + 3) & ~3;             // taps are consumed a dword (4 virtual angles) at a time
-        const int ac = acv / DUP;                   // first staged (real) angle of the chunk
-        const int na = (nav + DUP - 1) / DUP;       // staged rows
-        const int na_z = (na4 + DUP - 1) / DUP;     // rows a tap of this chunk may name
-        if (acv > 0) __syncthreads();
-        // a dead tap is byte 255: only cell 255 of every row (never a bin: PW <= 255) must hold 0.0f
-        auto stage_general = [&] {
-            if constexpr (NS == 1) {
-                stage_rows(lds, gs + (size_t)ac * g.PW, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
-            } else {
-                const float *srcs[NS];
-                chunk_srcs(ac, srcs);
-                stage_rows_interleaved<2>(lds, srcs, na, g.PW, g.PW, kBwdPitch, false, lane, wave, nwaves);
-            }
-        };
-        if constexpr (SHORT) {   // (na_z <= 32 rows: one store of the first lanes, issued while the rows are in flight)
-            auto zero_cells = [&] {
-                if ((int)threadIdx.x < na_z) reinterpret_cast<vec_t *>(lds)[threadIdx.x * kBwdPitch + 255] = 0.0f;
-            };
-            if (stage_magic != 0) {   // launch-uniform
-                const float *srcs[NS];
-                chunk_srcs(0, srcs);
-                stage_contig_rows<NS, 8 / NS>(lds, srcs, na, g.PW, kBwdPitch, stage_magic, threadIdx.x, blockDim.x, zero_cells);
-            } else {
-                zero_cells();
-            }
-        } else {
-            for (int t = threadIdx.x; t < na_z * NS; t += blockDim.x) lds[((t / NS) * kBwdPitch + 255) * NS + (t % NS)] = 0.0f;
-            if (ahead_valid) ahead.commit(lds, kBwdPitch);           // requested during the previous chunk's gathers
-            else stage_general();
-        }
-        ahead_valid = false;
-        if (kPipe && acv + chunk < VA) {            // wave-uniform
-            const float *srcs[NS];
-            chunk_srcs(ac + chunk / DUP, srcs);
-            const int nna = (min(chunk, VA - (acv + chunk)) + DUP - 1) / DUP;
-            if (StagedRows<NS, kPipe ? kAheadUnits : 1>::fits(srcs, nna, g.PW, g.PW, nwaves)) {
-                ahead.issue(srcs, nna, g.PW, g.PW, lane, wave, nwaves);
-                ahead_valid = true;
-            }
-        }
-        if (acv == 0) CTPVAE_PSTAMP(1);
-        __syncthreads();
-        if constexpr (SHORT) {
-            k0 = scale.at(s), k1 = has2 ? scale.at(s + 1) : 1.0f;
-            // Rows that stage_contig_rows cannot take (PW % 4 != 0, an unaligned tensor) go through the general stagers, and what a
-            // workgroup that is small for its rows could not request in one batch follows, BEHIND the barrier: the launches this form is
-            // written for run straight into their barrier and jump over this block.
-            const bool more = stage_magic != 0 && contig_rows_more<8 / NS>(na, g.PW, blockDim.x);
-            if (stage_magic == 0 || more) {   // launch-uniform
-                if (more) {
-                    const float *srcs[NS];
-                    chunk_srcs(0, srcs);
-                    stage_contig_rows_rest<NS, 8 / NS>(lds, srcs, na, g.PW, kBwdPitch, stage_magic, threadIdx.x, blockDim.x);
-                } else {
-                    stage_general();
-                }
-                __syncthreads();
-            }
-        }
-        if (acv == 0) CTPVAE_PSTAMP(2);
-        // up to four (eight with DUP = 2) groups of sixteen virtual angles, unrolled so that every row offset is an immediate
-        auto group = [&](auto al_tag) {
-            constexpr int AL = decltype(al_tag)::value;
-            if constexpr (AL < kChunk * DUP) {
-                if (AL >= na4) return;                       // wave-uniform
-                const int n_live = min(16, na4 - AL);
-                if constexpr (SHORT) {
-                    vec_t v[PPT][16];
-#pragma unroll
-#ifdef CTPVAE_TUNE_BWD_NOLDS
-                    for (int k = 0; k < PPT; ++k)   // timing only: no gathers, the index words stand in for the taps
-                        for (int e = 0; e < 16; ++e) v[k][e] = __uint_as_float((&q[0][k].x)[e & 3] & 0x3fffffu);
-#else
-                    for (int k = 0; k < PPT; ++k) gather16<AL, NS, DUP>(lds, q[0][k], n_live, v[k]);
-#endif
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) q[0][k] = q2nd[k];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[k] += v[k][e];   // skipped taps hold +0.0f
-                } else {
-                    // the chunks hold an even number of groups, so a group's slot in the two-deep index queue is a constant;
-                    // taps in two halves of eight (a wave holds at most 15 LDS operations in flight anyway): the registers of
-                    // the other half are what pays for the second index group
-                    constexpr int SLOT = (AL / 16) & 1;
-                    constexpr int ROW = kBwdPitch * 4 * NS;   // bytes per staged row
-                    // one index dword = four angles at a time for all PPT rows: PPT x 4 gathers in flight, added in angle order
-                    auto quarter = [&](auto d_tag) {
-                        constexpr int D = decltype(d_tag)::value;
-                        if (4 * D >= n_live) return;                 // wave-uniform: a partial last group skips whole dwords
-                        vec_t v[PPT][4];
-#pragma unroll
-                        for (int k = 0; k < PPT; ++k) {
-                            const unsigned w = D == 0 ? q[SLOT][k].x : D == 1 ? q[SLOT][k].y : D == 2 ? q[SLOT][k].z : q[SLOT][k].w;
-#ifdef CTPVAE_TUNE_BWD_NOLDS
-                            for (int e = 0; e < 4; ++e) v[k][e] = __uint_as_float(w & 0x3fffffu);
-#else
-                            int b0, b1, b2, b3;
-                            unpack4<NS == 1 ? 2 : 3>(w, b0, b1, b2, b3);
-                            v[k][0] = lds_at_vec<NS>(lds, b0 + ((AL + 4 * D + 0) / DUP) * ROW);
-                            v[k][1] = lds_at_vec<NS>(lds, b1 + ((AL + 4 * D + 1) / DUP) * ROW);
-                            v[k][2] = lds_at_vec<NS>(lds, b2 + ((AL + 4 * D + 2) / DUP) * ROW);
-                            v[k][3] = lds_at_vec<NS>(lds, b3 + ((AL + 4 * D + 3) / DUP) * ROW);
-#endif
-                        }
-                        if constexpr (D == 3) {   // this group's index vectors are consumed: request the group after next
-                            const int next = (acv + AL) / 16 + 2;
-                            if (next < L.NA16) load_group(next, std::integral_constant<int, SLOT>{});
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int k = 0; k < PPT; ++k)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[k] += v[k][e];
-                        __builtin_amdgcn_sched_barrier(0);
-                    };
-                    quarter(std::integral_constant<int, 0>{});
-                    quarter(std::integral_constant<int, 1>{});
-                    quarter(std::integral_constant<int, 2>{});
-                    quarter(std::integral_constant<int, 3>{});
-                    // (a partial group is the launch's last: nothing is requested behind it)
-                }
-            }
-        };
-        group(std::integral_constant<int, 0>{});
-        group(std::integral_constant<int, 16>{});
-        group(std::integral_constant<int, 32>{});
-        group(std::integral_constant<int, 48>{});
-        group(std::integral_constant<int, 64>{});
-        group(std::integral_constant<int, 80>{});
-        group(std::integral_constant<int, 96>{});
-        group(std::integral_constant<int, 112>{});
-    }
-    if (xcol < g.W) {
-#pragma unroll
-        for (int k = 0; k < PPT; ++k) {
-            const int y = y0 + k * nwaves;
-            if (y < g.H) {
-                if constexpr (NS == 1) {
-                    gimg[((size_t)s * g.H + y) * g.W + xcol] = k0 * acc[k];
-                } else {
-                    gimg[((size_t)s * g.H + y) * g.W + xcol] = k0 * acc[k].x;
-                    if (has2) gimg[((size_t)(s + 1) * g.H + y) * g.W + xcol] = k1 * acc[k].y;
-                }
-            }
-        }
-    }
-    CTPVAE_PSTAMP(3);
-}
+// (the kernel's text: rotate_bwd_planned_kernel.h, compiled once per store policy of the gradient image; of the write-through text only
+// the SHORT forms are launched, so only they are instantiated -- launch_bwd_planned's rule)
+#define CTPVAE_BWD_PLANNED_KERNEL rotate_bwd_planned_kernel
+#define CTPVAE_BWD_PLANNED_STORE kStorePlain
+#include "rotate_bwd_planned_kernel.h"
+#undef CTPVAE_BWD_PLANNED_KERNEL
+#undef CTPVAE_BWD_PLANNED_STORE
+#define CTPVAE_BWD_PLANNED_KERNEL rotate_bwd_planned_kernel_wt
+#define CTPVAE_BWD_PLANNED_STORE kStoreWriteThrough
+#include "rotate_bwd_planned_kernel.h"
+#undef CTPVAE_BWD_PLANNED_KERNEL
+#undef CTPVAE_BWD_PLANNED_STORE
 
 // ---- angle-selecting planned backward ("bwd4" plan) ---------------------------------------------------------------------
 // The 16-angles-per-vector plan above cannot project a SUBSET of its angles (the training loop's per-step `api` random
@@ -1744,12 +1505,25 @@ static int launch_bwd_planned(const float *gsino_dev, int S, int H, int W, int P
                            inv_tiles, inv_nxb, stage_magic);
         return CTPVAE_OK;
     };
+    // The gradient image's stores.  A launch ends by writing its dirty L2 lines back (3.28 MB of them at the headline batch) before a
+    // dependent launch may start; write-through (sc1) stores send them out while the kernel still runs.  Measured per kernel, parent and
+    // change alternated on one box (profiles/r14_wt_stores_ab.txt): the SHORT forms gain 0.31 us of 4.73 at the
+    // headline batch (every run below every run of the parent, 6 x its spread), 1.07 us of 7.95 with a reader of the gradient behind the
+    // launch, and are level at B = 1 and 5: write-through.  The general form (more than 32 angles) gained 0.21 us of 16.9 at 1.1 x the
+    // spread: it keeps plain stores and has no twin, nor have the exact-transpose plan's launches.  Non-temporal stores gained less than
+    // write-through on both (0.13 us; nothing with the reader): no kernel has that form, knob WT_STORES = 2 runs the plain ones.
+    const int st = is_short ? store_policy(kStoreWriteThrough) : kStorePlain;
     int rc;
     if (dup == 2) {
         if (ns == 2)
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<2, 256, 2, 2>) : launch(rotate_bwd_planned_kernel<2, 1024, 2, 2>);
         else
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<4, 256, 1, 2>) : launch(rotate_bwd_planned_kernel<4, 1024, 1, 2>);
+    } else if (is_short && st == kStoreWriteThrough) {   // (the SHORT forms' write-through twins)
+        if (ns == 2)
+            rc = waves <= 4 ? launch(rotate_bwd_planned_kernel_wt<2, 256, 2, 1, true>) : launch(rotate_bwd_planned_kernel_wt<2, 1024, 2, 1, true>);
+        else
+            rc = waves <= 4 ? launch(rotate_bwd_planned_kernel_wt<4, 256, 1, 1, true>) : launch(rotate_bwd_planned_kernel_wt<4, 1024, 1, 1, true>);
     } else if (is_short) {   // two index groups at most: both requested up front
         if (ns == 2)
             rc = waves <= 4 ? launch(rotate_bwd_planned_kernel<2, 256, 2, 1, true>) : launch(rotate_bwd_planned_kernel<2, 1024, 2, 1, true>);
