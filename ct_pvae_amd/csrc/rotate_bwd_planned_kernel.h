@@ -143,6 +143,9 @@ __global__ __launch_bounds__(MAXT) void CTPVAE_BWD_PLANNED_KERNEL(const float *_
                 ahead_valid = true;
             }
         }
+        // (the gradient image's address is asked for with the other launch constants: left to the compiler, its scalar load sinks to the
+        // stores, where a CU's first workgroup waits out a cold scalar-cache miss with nothing left to hide it)
+        if constexpr (SHORT) asm volatile("" ::"s"(gimg));
         if (acv == 0) CTPVAE_PSTAMP(1);
         __syncthreads();
         if constexpr (SHORT) {
@@ -163,29 +166,53 @@ __global__ __launch_bounds__(MAXT) void CTPVAE_BWD_PLANNED_KERNEL(const float *_
             }
         }
         if (acv == 0) CTPVAE_PSTAMP(2);
+        if constexpr (SHORT) {
+            // The launch's na4 / 4 = 1 .. 8 index dwords, each executed as what it is: T dwords of the index vectors qq (staged rows
+            // AL .. AL + 4 T - 1) are 4 T unpacks, gathers and, behind them, adds per owned row -- straight-line code per T, no
+            // register zeroed to stand in for a tap the launch does not have.  (The accumulators start at +0.0f and can therefore
+            // never be -0.0f: an add of +0.0f that is not executed changes no bit.)
+            auto taps = [&](auto al_tag, auto t_tag, const uint4(&qq)[PPT]) {
+                constexpr int AL = decltype(al_tag)::value, T = decltype(t_tag)::value;
+                vec_t v[PPT][4 * T];
+#pragma unroll
+#ifdef CTPVAE_TUNE_BWD_NOLDS
+                for (int k = 0; k < PPT; ++k)   // timing only: no gathers, the index words stand in for the taps
+                    for (int e = 0; e < 4 * T; ++e) v[k][e] = __uint_as_float((&qq[k].x)[e & 3] & 0x3fffffu);
+#else
+                for (int k = 0; k < PPT; ++k) gather_dwords<AL, T, NS>(lds, qq[k], v[k]);
+#endif
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int e = 0; e < 4 * T; ++e)   // ascending angle; the rows' sums side by side: no add waits for the one before it
+#pragma unroll
+                    for (int k = 0; k < PPT; ++k) acc[k] += v[k][e];
+                // (a case ends in a line of its own: the cases' last adds look alike, and the compiler's branch folder would otherwise
+                // share them in one block behind one more jump)
+                asm volatile("; rows %0 .. of %1 dwords" ::"n"(AL), "n"(T));
+            };
+            // the last 1 .. 4 dwords, read from the second index vectors (which ARE the first when there is one group): one
+            // wave-uniform branch into the four cases
+            auto tail = [&](auto al_tag) {
+                const int r = na4 - decltype(al_tag)::value;   // 4, 8, 12 or 16 taps
+                if (r < 8) taps(al_tag, std::integral_constant<int, 1>{}, q2nd);
+                else if (r < 12) taps(al_tag, std::integral_constant<int, 2>{}, q2nd);
+                else if (r < 16) taps(al_tag, std::integral_constant<int, 3>{}, q2nd);
+                else taps(al_tag, std::integral_constant<int, 4>{}, q2nd);
+            };
+            if (na4 <= 16) {                                 // launch-uniform
+                tail(std::integral_constant<int, 0>{});
+            } else {
+                taps(std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{}, q[0]);
+                tail(std::integral_constant<int, 16>{});
+            }
+        }
         // up to four (eight with DUP = 2) groups of sixteen virtual angles, unrolled so that every row offset is an immediate
         auto group = [&](auto al_tag) {
             constexpr int AL = decltype(al_tag)::value;
-            if constexpr (AL < kChunk * DUP) {
+            if constexpr (!SHORT && AL < kChunk * DUP) {
                 if (AL >= na4) return;                       // wave-uniform
                 const int n_live = min(16, na4 - AL);
-                if constexpr (SHORT) {
-                    vec_t v[PPT][16];
-#pragma unroll
-#ifdef CTPVAE_TUNE_BWD_NOLDS
-                    for (int k = 0; k < PPT; ++k)   // timing only: no gathers, the index words stand in for the taps
-                        for (int e = 0; e < 16; ++e) v[k][e] = __uint_as_float((&q[0][k].x)[e & 3] & 0x3fffffu);
-#else
-                    for (int k = 0; k < PPT; ++k) gather16<AL, NS, DUP>(lds, q[0][k], n_live, v[k]);
-#endif
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k) q[0][k] = q2nd[k];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int k = 0; k < PPT; ++k)
-#pragma unroll
-                        for (int e = 0; e < 16; ++e) acc[k] += v[k][e];   // skipped taps hold +0.0f
-                } else {
+                {
                     // the chunks hold an even number of groups, so a group's slot in the two-deep index queue is a constant;
                     // taps in two halves of eight (a wave holds at most 15 LDS operations in flight anyway): the registers of
                     // the other half are what pays for the second index group

@@ -790,27 +790,24 @@ template <int NS> __device__ __forceinline__ typename SliceVec<NS>::type lds_at_
 {
     return *(const __attribute__((address_space(3))) typename SliceVec<NS>::type *)(size_t)(unsigned)byte_off;   // see lds_at
 }
-// the 16 taps of `q` are staged rows AL0 .. AL0+15: the row offset is a compile-time ds_read immediate, the address
-// VGPR is just the SDWA-extracted bin * cell size -- no address arithmetic per tap
-template <int AL0, int NS, int DUP = 1>
-__device__ __forceinline__ void gather16(const float *lds, const uint4 q, int n_live, typename SliceVec<NS>::type (&v)[16])
+// the 4 T taps of the first T dwords of `q` are staged rows AL0 .. AL0+4T-1: the row offset is a compile-time ds_read immediate, the
+// address VGPR is just the SDWA-extracted bin * cell size -- no address arithmetic per tap.  T is a constant: a launch whose last index
+// vector has fewer than four live dwords runs the code of that many (the SHORT form of the planned backward), and nothing stands in
+// for the others.
+template <int AL0, int T, int NS>
+__device__ __forceinline__ void gather_dwords(const float *lds, const uint4 q, typename SliceVec<NS>::type (&v)[4 * T])
 {
-    // DUP = 2 (exact-transpose plan): taps AL0 + e are "virtual angles"; virtual angle v reads staged row v / 2
-    // n_live (wave-uniform): staged rows AL0 .. AL0+n_live-1 exist; a partial last group skips whole dwords of taps
+    static_assert(T >= 1 && T <= 4, "an index vector is four dwords");
     constexpr int ROW = kBwdPitch * 4 * NS;   // bytes per staged row
     const unsigned w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        if (4 * d < n_live) {
-            int b0, b1, b2, b3;
-            unpack4<NS == 1 ? 2 : 3>(w[d], b0, b1, b2, b3);
-            v[4 * d + 0] = lds_at_vec<NS>(lds, b0 + ((AL0 + 4 * d + 0) / DUP) * ROW);
-            v[4 * d + 1] = lds_at_vec<NS>(lds, b1 + ((AL0 + 4 * d + 1) / DUP) * ROW);
-            v[4 * d + 2] = lds_at_vec<NS>(lds, b2 + ((AL0 + 4 * d + 2) / DUP) * ROW);
-            v[4 * d + 3] = lds_at_vec<NS>(lds, b3 + ((AL0 + 4 * d + 3) / DUP) * ROW);
-        } else {
-            v[4 * d + 0] = v[4 * d + 1] = v[4 * d + 2] = v[4 * d + 3] = 0.0f;
-        }
+    for (int d = 0; d < T; ++d) {
+        int b0, b1, b2, b3;
+        unpack4<NS == 1 ? 2 : 3>(w[d], b0, b1, b2, b3);
+        v[4 * d + 0] = lds_at_vec<NS>(lds, b0 + (AL0 + 4 * d + 0) * ROW);
+        v[4 * d + 1] = lds_at_vec<NS>(lds, b1 + (AL0 + 4 * d + 1) * ROW);
+        v[4 * d + 2] = lds_at_vec<NS>(lds, b2 + (AL0 + 4 * d + 2) * ROW);
+        v[4 * d + 3] = lds_at_vec<NS>(lds, b3 + (AL0 + 4 * d + 3) * ROW);
     }
 }
 
@@ -851,7 +848,10 @@ __device__ __forceinline__ void gather8(const float *lds, unsigned w0, unsigned 
 // constants, its block number is decoded with the mended multiplications of div_by_magic_floor (inv_tiles, inv_nxb are then
 // div_magic_floor words: no division behind them, knob NO_MAGIC does not apply), the wave number is a scalar, and the cotangent rows go
 // through stage_contig_rows (stage_magic != 0: the host found PW % 4 == 0 and a 16-byte aligned tensor) with the dead taps' zero cells
-// written while the loads fly; otherwise through the general stagers.
+// written while the loads fly; otherwise through the general stagers.  Behind the barrier the phase is bound by the instructions four
+// waves issue on a SIMD, so a SHORT launch runs the code of the index dwords it HAS: the full vector of sixteen taps as straight-line
+// code when A > 16, then one of four straight-line cases for the 1 .. 4 dwords of its tail (gather_dwords) -- no slot that is jumped
+// over and zero-filled, no add of a zero (profiles/r15_bwd_short_gather_isa.txt, tools/count_bwd_gather_isa.py).
 // (the kernel's text: rotate_bwd_planned_kernel.h, compiled once per store policy of the gradient image; of the write-through text only
 // the SHORT forms are launched, so only they are instantiated -- launch_bwd_planned's rule)
 #define CTPVAE_BWD_PLANNED_KERNEL rotate_bwd_planned_kernel
