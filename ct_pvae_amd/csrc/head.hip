@@ -40,77 +40,15 @@
 // A quad is moved with one 16-byte access when it is whole and 16-byte aligned in memory (object offset o * pix a multiple of 4,
 // pointers 16-byte aligned), with guarded 4-byte accesses otherwise.  The backward has no sum: it walks the n * pix pixels as
 // memory quads, 256 threads per workgroup.
-#include <climits>
-#include <initializer_list>
-
-#include "common.h"
-#include "loglik_math.h"
-#include "philox.h"
-#include "quad_io.h"
+//
+// The pixel's function, its constants and the Philox layout live in tn_head.h, which marginals.hip shares.
+#include "tn_head.h"
 
 namespace ctpvae {
 
-constexpr unsigned kHeadTag = 0x544E48u;     // "TNH": the fourth counter word (hmc.hip: 0x484D43, poisson.hip: 0)
+static_assert(kHeadTag == 0x544E48u, "kHeadTag = 0x544E48u is part of the stream's definition (include/ctpvae_radon.h)");
 constexpr int kHeadFwdThreads = kObjectSumThreads;
 constexpr int kHeadBwdThreads = 256;
-constexpr float kHeadEps = 1.1920928955078125e-07f;    // FLT_EPSILON, positive_range's offset
-constexpr float kHeadPLo = 1e-7f;
-constexpr float kHeadQLo = 1.1920928955078125e-07f;    // 1 - HI, HI = (float)(1 - 1e-7) = 1 - 2^-23
-constexpr float kInvSqrt2 = 0.70710678118654752440f;
-constexpr float kSqrt2Pi = 2.50662827463100050242f;
-constexpr float kInvSqrt2Pi = 0.39894228040143267794f;
-
-__host__ __device__ inline float head_u24(unsigned w) { return ((float)(w >> 8) + 0.5f) * 5.9604644775390625e-08f; }
-
-__host__ __device__ inline Philox4 head_block(unsigned long long blk, unsigned draw, unsigned k0, unsigned k1)
-{
-    return philox4x32_10((unsigned)blk, (unsigned)(blk >> 32), draw, kHeadTag, k0, k1);
-}
-// the uniforms of the four pixels e .. e+3 (one block when e is a multiple of 4, two otherwise)
-__device__ __forceinline__ void head_uniforms4(unsigned long long e, unsigned draw, unsigned k0, unsigned k1, float (&u)[4])
-{
-    const unsigned s = (unsigned)e & 3u;
-    const Philox4 A = head_block(e >> 2, draw, k0, k1);
-    Philox4 B = A;
-    if (s != 0) B = head_block((e >> 2) + 1, draw, k0, k1);
-#pragma unroll
-    for (unsigned j = 0; j < 4; ++j) u[j] = head_u24(s + j < 4 ? philox_word(A, s + j) : philox_word(B, s + j - 4));
-}
-
-struct TnPixel {
-    float scale, dloc, dscale;   // pr(beta), pr'(alpha), pr'(beta)
-    float a, Z, omu, z, D;       // D = ndtri'(p) (backward only)
-    float x, zeta, lp;
-    bool pass_p, pass_x;         // the clamps of p and of x let the gradient through
-};
-
-template <bool BWD>
-__device__ __forceinline__ TnPixel tn_pixel(float alpha, float beta, float u)
-{
-    TnPixel r;
-    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
-    const float loc = alpha >= 1.0f ? alpha : ea + kHeadEps;
-    r.scale = beta >= 1.0f ? beta : eb + kHeadEps;
-    r.dloc = alpha >= 1.0f ? 1.0f : ea;
-    r.dscale = beta >= 1.0f ? 1.0f : eb;
-    r.a = -loc / r.scale;
-    const float t = r.a * kInvSqrt2;
-    const float Pa = 0.5f * erfcf(-t);
-    r.Z = fmaxf(0.5f * erfcf(t), 1e-30f);
-    r.omu = 1.0f - u;
-    const float p0 = Pa + u * r.Z, q0 = r.Z * r.omu;
-    const bool upper = p0 > 0.5f;
-    r.pass_p = upper ? q0 >= kHeadQLo : p0 >= kHeadPLo;
-    const float zt = normcdfinvf(upper ? fmaxf(q0, kHeadQLo) : fmaxf(p0, kHeadPLo));
-    r.z = upper ? -zt : zt;
-    const float x0 = loc + r.scale * r.z;
-    r.pass_x = x0 >= 0.0f;
-    r.x = fmaxf(x0, 0.0f);
-    r.zeta = (r.x - loc) / r.scale;
-    r.lp = ((-0.5f * (r.zeta * r.zeta) - kHalfLog2Pi) - logf(r.scale)) - logf(r.Z);
-    if constexpr (BWD) r.D = kSqrt2Pi * expf(0.5f * (r.z * r.z));
-    return r;
-}
 
 struct HeadRng {
     unsigned long long first_pixel;   // first_object * pix
@@ -187,23 +125,6 @@ __global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const floa
     }
     quad_store(g_alpha, i, cnt, vec, ga);
     quad_store(g_beta, i, cnt, vec, gb);
-}
-
-static int head_check(const char *what, const void *alpha, const void *beta, int n, int pix, long long first_object)
-{
-    CTPVAE_REQUIRE(alpha && beta, "%s: null pointer", what);
-    CTPVAE_REQUIRE(n > 0 && pix > 0, "%s: sizes must be positive (n=%d pix=%d)", what, n, pix);
-    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "%s: n * pix must fit 31 bits (n=%d pix=%d)", what, n, pix);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
-                   "%s: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", what, first_object);
-    return CTPVAE_OK;
-}
-
-static bool head_aligned16(std::initializer_list<const void *> ptrs)
-{
-    for (const void *p : ptrs)
-        if (((size_t)p & 15) != 0) return false;   // (a null pointer counts as aligned)
-    return true;
 }
 
 }  // namespace ctpvae

@@ -39,6 +39,7 @@ from .fbp import iradon_all
 from .forward_functions import num_proj_pix
 from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
 from .latents import normal_latents
+from .marginals import PixelMarginals
 from .output_head import truncated_normal_head
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -337,6 +338,10 @@ class AngleStream:
         return out
 
 
+_PIXEL_DIST_NEEDS = ("--pixel_dist samples the TruncatedNormal output head of sampled Normal latents: it needs --normal and cannot be "
+                     "combined with --det (the Beta head is not sampled by any kernel)")
+
+
 class PVAETrainer:
     def __init__(self, args, device):
         self.args, self.dev = args, device
@@ -344,6 +349,8 @@ class PVAETrainer:
             raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
         if getattr(args, "fused_latents", False) and (not args.use_normal or args.deterministic):
             raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
+        if getattr(args, "pixel_dist", False) and (not args.use_normal or args.deterministic):
+            raise ValueError(_PIXEL_DIST_NEEDS)
         self.world, self.rank, _ = sharding.env_world()
         self.sqrt_reg = EPS32
         # the nets' shapes are static: --miopen_find lets MIOpen search its convolution algorithms once (14.9 -> 11.5 ms
@@ -607,6 +614,51 @@ class PVAETrainer:
             np.save(os.path.join(save_path, "reconstruction_final.npy"), reconstruction_final)
         return loss_final, reconstruction_final
 
+    @torch.no_grad()
+    def pixel_dist(self, example_num=0, num_repeats=10000, num_samples_1=100, save_path=None, bins=50, lo=0.005, width=0.01):
+        """CT_VAE.pixel_dist (ctvae/main_ct_vae.py:648-731) without its figures: the per-pixel marginals of the network's posterior for
+        one example.  The example's encoder input is repeated `-b` times (load_batch, :635-646); every repeat r draws `ns` latent
+        samples per copy, decodes them and adds num_samples_1 draws of the output head per decoder output to a PixelMarginals
+        (seed = --head_seed, draws r * num_samples_1 ..): num_repeats * ns * b * num_samples_1 samples per pixel, none of them stored.
+        With --fused_latents the latents are normal_latents' keyed by (--head_seed, draw = r); without it they come from torch's
+        global generator as in find_loss_vae_unsup.  The encoder does not depend on r and runs once; the projector and the likelihood,
+        which the reference computes and discards, are not called.  Only rank 0 runs it: it writes <save_path>/pixel_dist_<en>.npz,
+        prints one line and returns the PixelMarginals (the other ranks return None)."""
+        a = self.args
+        if not a.use_normal or a.deterministic:
+            raise ValueError(_PIXEL_DIST_NEEDS)
+        example_num, num_repeats = int(example_num), int(num_repeats)
+        if not 0 <= example_num < self.input_encode.shape[0]:
+            raise ValueError(f"pixel_dist: example {example_num} is not one of the {self.input_encode.shape[0]} examples")
+        if num_repeats < 1:
+            raise ValueError(f"pixel_dist: num_repeats must be >= 1 (got {num_repeats})")
+        if self.rank != 0:
+            return None
+        ns, B = int(a.ns), a.batch_size
+        fused = bool(getattr(a, "fused_latents", False))
+        skips = self.enc(self.input_encode[example_num:example_num + 1].repeat(B, 1, 1, 1) / 300)
+        if fused:
+            skips = [sk.contiguous() for sk in skips]
+        else:
+            q = [(loc.repeat(ns, 1, 1, 1), (positive_range(log_scale) + self.sqrt_reg).repeat(ns, 1, 1, 1))
+                 for loc, log_scale in (sk.chunk(2, dim=1) for sk in skips)]
+        m = PixelMarginals((self.x_size, self.y_size), bins=bins, lo=lo, width=width, device=self.dev)
+        for r in range(num_repeats):
+            if fused:
+                q_sample = [normal_latents(sk, ns=ns, seed=a.head_seed, draw=r, level=level, first_object=0, sqrt_reg=self.sqrt_reg)[0]
+                            for level, sk in enumerate(skips)]
+            else:
+                q_sample = [loc + scale * torch.randn_like(loc) for loc, scale in q]
+            alpha, beta = self.dec(q_sample)
+            m.add(alpha.contiguous(), beta.contiguous(), draws=num_samples_1, seed=a.head_seed, draw0=r * num_samples_1)
+        if save_path is not None:
+            os.makedirs(save_path, exist_ok=True)
+            m.save(os.path.join(save_path, f"pixel_dist_{example_num}.npz"))
+        mean = m.mean()
+        print(f"pixel_dist example {example_num}: {m.count} samples per pixel, per-pixel means {float(mean.min()):.6f} .. "
+              f"{float(mean.max()):.6f}", flush=True)
+        return m
+
 
 def get_args(argv=None):
     """The reference's flags that reach the path (ctvae/main_ct_vae.py:30-116), same spellings and defaults."""
@@ -668,6 +720,14 @@ def get_args(argv=None):
     p.add_argument("--no_pad", action="store_true", help="sinograms have no zero-padding (ctvae/main_ct_vae.py:107)")
     p.add_argument("--toy_masks", action="store_true", help="the toy problem's two-angle masks (ctvae/main_ct_vae.py:109)")
     p.add_argument("--no_final_eval", action="store_true", help="skip the final evaluation (ctvae/main_ct_vae.py:113)")
+    p.add_argument("--pixel_dist", action="store_true",
+                   help="per-pixel marginals of the network's posterior for example --en (ctvae/main_ct_vae.py:103, CT_VAE.pixel_dist): "
+                        "a histogram and two moments per pixel over --pixel_repeats decoder passes of 100 draws each, written to "
+                        "<save_path>/pixel_dist_<en>.npz (csrc/marginals.hip; no sample is stored); needs --normal, not with --det")
+    p.add_argument("--en", type=int, dest="example_num", default=0, help="the example --pixel_dist looks at")
+    p.add_argument("--pixel_repeats", type=int, default=10000,
+                   help="decoder passes of --pixel_dist, each over -b copies of the example and --ns latent samples (the reference's "
+                        "hard-coded 10000)")
     p.add_argument("--se", type=int, dest="stride_encode", default=2)
     p.add_argument("--si", type=int, dest="si", default=100000)
     p.add_argument("--miopen_find", action="store_true",
@@ -686,6 +746,8 @@ def get_args(argv=None):
         raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
     if args.fused_latents and (not args.use_normal or args.deterministic):
         raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
+    if args.pixel_dist and (not args.use_normal or args.deterministic):
+        raise ValueError(_PIXEL_DIST_NEEDS)
     return args
 
 
@@ -697,6 +759,8 @@ def main(argv=None):
     if args.restore:                                   # ctvae/main_ct_vae.py:363-368 (--ulc: the latest checkpoint)
         tr.restore(tr.latest_checkpoint())
     losses, secs = tr.train() if args.train else ([], 0.0)
+    if args.pixel_dist:                                # ctvae/main_ct_vae.py: the trained (or restored) network's pixel marginals
+        tr.pixel_dist(example_num=args.example_num, num_repeats=args.pixel_repeats, save_path=args.save_path)
     if not args.no_final_eval:
         loss_final, _ = tr.final_evaluation(args.save_path)
         if rank == 0:

@@ -715,6 +715,29 @@ int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n,
                            float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream);
 int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host);
 
+/* ---- per-pixel marginals of the TruncatedNormal output head (the reference's CT_VAE.pixel_dist, ctvae/main_ct_vae.py:648-731): the
+ * histogram, the sum and the sum of squares of the samples of every pixel, with no sample written to memory (csrc/marginals.hip
+ * states the layout and the fixed order of the float64 sums).  alpha_dev, beta_dev [n][pix] as for ctpvae_tn_head_fwd_f32.  The launch
+ * covers the n * pix * draws samples (o, pixel, k), k < draws: each IS, bit for bit, the x that ctpvae_tn_head_fwd_f32 writes for that
+ * object and pixel with draw = draw0 + k and the same seed and first_object.  All n objects are samples of the SAME pix pixels.
+ *   Bin of a sample x, in fp32: t = (x - lo) / width (one subtraction, one correctly rounded division); column 0 if !(t >= 0) (NaN
+ *   too), column bins + 1 if t >= bins, otherwise column 1 + (int)t.
+ *   State, caller-owned, on the device, ADDED to (zero it first; any number of launches on one stream is well defined):
+ *     hist_dev [pix][bins + 2] int64 counts;  s1_dev, s2_dev [pix] float64: the sum of the samples and of their squares, each fp32
+ *     sample widened to double first.  Counts are combined with integer atomics; the float64 sums use no floating-point atomics and a
+ *     fixed order, so one sequence of calls gives one set of bits in all three.
+ *   _workspace_bytes: bytes of workspace_dev for (n, pix, draws): at most 1024 * pix, whatever draws is.  The workspace carries
+ *     nothing between calls.
+ *   _bin_host_f32: the bin rule applied to count values in HOST memory, columns into col_out_host [count]; needs no GPU.
+ * 1 <= bins <= CTPVAE_MARGINALS_MAX_BINS; width > 0, lo and width finite; draws >= 1, draw0 + draws <= 2^32, n * draws < 2^32;
+ * n * pix <= 2^31 - 1; first_object >= 0; state and workspace 8-byte aligned. */
+#define CTPVAE_MARGINALS_MAX_BINS 254
+long long ctpvae_tn_marginals_workspace_bytes(int n, int pix, unsigned draws);
+int ctpvae_tn_marginals_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                            unsigned long long seed, unsigned draw0, unsigned draws, float lo, float width, int bins,
+                            long long *hist_dev, double *s1_dev, double *s2_dev, void *workspace_dev, ctpvae_stream_t stream);
+int ctpvae_tn_marginals_bin_host_f32(const float *x_host, long long count, float lo, float width, int bins, int *col_out_host);
+
 /* ---- the P-VAE's Normal latent block at one skip level (ctvae/helper_functions.py:247-252, :267, :325-327): the ns reparameterised
  * samples, the KL term against N(0, 1) and its per-object sum in ONE launch, their gradients in one more (csrc/latent.hip states the
  * function, the order of the sum and the layout of the random numbers).  skip_dev [B][2][len]: the encoder's output at the level,
