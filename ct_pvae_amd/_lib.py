@@ -174,6 +174,10 @@ SIGNATURES = {
     "ctpvae_periodic_pad_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ctpvae_maxout_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "ctpvae_maxout_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
+    "ctpvae_merit_tile": (_c_int, []),
+    "ctpvae_merit_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
+    "ctpvae_merit_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_merit_f64": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
 }
 
 _lib = None

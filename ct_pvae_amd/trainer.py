@@ -421,6 +421,7 @@ class PVAETrainer:
                                                     toy_masks=a.toy_masks,
                                                     truncate_dataset=a.td, device=dev)
         self.masks, self.truth = masks, (torch.from_numpy(imgs).to(dev) if imgs is not None else None)
+        self.sinograms = sino if getattr(a, "final_merit", False) else None           # the clean sinograms, kept for --final_merit only
         # initial reconstructions for the encoder, ctvae/helper_functions.py:477-529 with FBP on the GPU
         enc_in = iradon_all(self.proj_samples, masks, self.P, self.theta_np, list(a.algorithms), self.sqrt_reg, self.x_size,
                             self.y_size, save_path=save_here, train=drawing)          # [td][X][Y][len(algorithms) + 1]
@@ -614,6 +615,21 @@ class PVAETrainer:
             np.save(os.path.join(save_path, "reconstruction_final.npy"), reconstruction_final)
         return loss_final, reconstruction_final
 
+    def final_merit(self, save_path, ground_truth=None, seed=0):
+        """bin/final_merit.py on what final_evaluation left under save_path (ct_pvae_amd/final_merit.py), when a ground truth is
+        known: the synthetic set's phantoms, or `ground_truth` (a .npy path or an array).  The two baselines are reconstructed with
+        gridrec, as the reference script and the command line do, whatever --algorithms feeds the encoder.  Needs --final_merit (the
+        clean sinograms are kept for it).  Returns final_merit's result, or None (with a note) when there is no ground truth."""
+        from .final_merit import final_merit
+        if self.sinograms is None:
+            raise ValueError("PVAETrainer.final_merit: the trainer was made without --final_merit, so the clean sinograms were not kept")
+        truth = ground_truth if ground_truth is not None else self.truth
+        if truth is None:
+            print("--final_merit: no ground truth is known for this dataset (pass --ground_truth FILE); nothing scored")
+            return None
+        return final_merit(self.args.input_path, save_path, self.args.pnm, ground_truth=truth, algorithm="gridrec", seed=seed,
+                           dataset=(self.sinograms, self.theta_np), device=self.dev)
+
     @torch.no_grad()
     def pixel_dist(self, example_num=0, num_repeats=10000, num_samples_1=100, save_path=None, bins=50, lo=0.005, width=0.01):
         """CT_VAE.pixel_dist (ctvae/main_ct_vae.py:648-731) without its figures: the per-pixel marginals of the network's posterior for
@@ -720,6 +736,12 @@ def get_args(argv=None):
     p.add_argument("--no_pad", action="store_true", help="sinograms have no zero-padding (ctvae/main_ct_vae.py:107)")
     p.add_argument("--toy_masks", action="store_true", help="the toy problem's two-angle masks (ctvae/main_ct_vae.py:109)")
     p.add_argument("--no_final_eval", action="store_true", help="skip the final evaluation (ctvae/main_ct_vae.py:113)")
+    p.add_argument("--final_merit", action="store_true",
+                   help="after the final evaluation, score reconstruction_final.npy the reference's way (bin/final_merit.py, "
+                        "ct_pvae_amd/final_merit.py): <save_path>/final_ave_merit.npy, the 3 x 3 table of MSE / SSIM / PSNR, the two baselines "
+                        "reconstructed with gridrec as in the reference (not with --algorithms); needs "
+                        "--save_path and a ground truth: the synthetic set's own phantoms, or --ground_truth with --input_path")
+    p.add_argument("--ground_truth", default=None, help="ground-truth images [n][X][Y] (.npy) of an --input_path dataset, for --final_merit")
     p.add_argument("--pixel_dist", action="store_true",
                    help="per-pixel marginals of the network's posterior for example --en (ctvae/main_ct_vae.py:103, CT_VAE.pixel_dist): "
                         "a histogram and two moments per pixel over --pixel_repeats decoder passes of 100 draws each, written to "
@@ -748,6 +770,9 @@ def get_args(argv=None):
         raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
     if args.pixel_dist and (not args.use_normal or args.deterministic):
         raise ValueError(_PIXEL_DIST_NEEDS)
+    if args.final_merit and (not args.save_path or args.no_final_eval):
+        raise ValueError("--final_merit scores the final evaluation's reconstruction_final.npy: it needs --save_path and cannot be "
+                         "combined with --no_final_eval")
     return args
 
 
@@ -765,6 +790,8 @@ def main(argv=None):
         loss_final, _ = tr.final_evaluation(args.save_path)
         if rank == 0:
             print(f"Average loss final : {float(loss_final.mean()):.6f}")
+        if args.final_merit and rank == 0:
+            tr.final_merit(args.save_path, ground_truth=args.ground_truth)
     if rank == 0:
         mse, mse_fbp = tr.evaluate()
         if losses:

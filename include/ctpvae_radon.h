@@ -782,6 +782,24 @@ int ctpvae_periodic_pad_bwd_f32(const float *g_dev, int planes, int H, int W, in
 int ctpvae_maxout_fwd_f32(const float *y_dev, int n, int len, float *out_dev, unsigned char *first_out_dev, ctpvae_stream_t stream);
 int ctpvae_maxout_bwd_f32(const float *g_dev, const unsigned char *first_dev, int n, int len, float *gy_out_dev, ctpvae_stream_t stream);
 
+/* ---- (MSE, SSIM, PSNR) of a batch of image pairs in float64 (the reference's compare, ctvae/helper_functions.py:394-418, with
+ * scikit-image 0.18's structural_similarity: uniform window, K1 0.01, K2 0.03, sample covariance, the data range taken from the
+ * reference image); added at ABI 3400.  ref_dev, test_dev [n][X][Y] contiguous, both float (_f32; widened to double first) or both
+ * double (_f64); out_dev [n][3] float64 = (mse, ssim, psnr) of test[k] against ref[k].  csrc/merit.hip states every operation and the
+ * one order of every sum: three launches whatever n, X, Y are, no floating-point atomics, no S map in memory; the same call gives the
+ * same bits on every run and pair k's numbers do not depend on n or k.  win = 7 if min(X, Y) >= 7, else the largest odd number
+ * <= min(X, Y); psnr = +inf where mse == 0; non-finite pixels propagate as in numpy's formula.
+ *   _tile: the edge of a tile of window positions (a workgroup of the SSIM launch covers tile x tile positions; host only).
+ *   _workspace_bytes: bytes of workspace_dev (8-byte aligned) for (n, X, Y): at most 32 * n * ceil((X - win + 1) / tile) *
+ *     ceil((Y - win + 1) / tile); 0 for n = 0.  The workspace carries nothing between calls.
+ * Every check is made before any launch: n >= 0 (n = 0: nothing is launched, CTPVAE_OK); X, Y >= 3; n * X * Y <= 2^31 - 1. */
+int ctpvae_merit_tile(void);
+long long ctpvae_merit_workspace_bytes(int n, int X, int Y);
+int ctpvae_merit_f32(const float *ref_dev, const float *test_dev, int n, int X, int Y, void *workspace_dev, double *out_dev,
+                     ctpvae_stream_t stream);
+int ctpvae_merit_f64(const double *ref_dev, const double *test_dev, int n, int X, int Y, void *workspace_dev, double *out_dev,
+                     ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
