@@ -380,24 +380,41 @@ constexpr int kSelRounds = 4;
 // gathered into va and reloaded), va, vb, acc.
 // (round 4: the task's last group issues nothing behind it -- the gathers of a group past the last were ~7 % of the
 // launch's LDS instructions)
-#define CTPVAE_PSTEP(LAST, QN, VN, VC, LOADNEXT)                                                   \
-                if (LAST >= ng) {   /* VC is the last group: added behind the loop (see cplan_walk.h cwalk) */ \
-                    _Pragma("unroll") for (int e = 0; e < 8; ++e) vt[e] = VC[e];                    \
-                    break;                                                                         \
-                }                                                                                  \
+// The steady-state loop has ONE exit, at its end, and takes whole trips of four groups; the last one to four groups are added behind
+// it by a chain of ifs.  With a `break` per group (the form until round 16) hipcc gave the loop one latch that every break passed
+// through on its way out, the wait inserter met at the loop header the state of each of them -- an index vector and eight gathers
+// just issued -- and opened every trip with s_waitcnt vmcnt(0) lgkmcnt(0): the four-deep index stream ran one deep
+// (profiles/r16_fwd_walk_waits_isa.txt).
+#define CTPVAE_PADD(VC) _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += VC[e];
+#define CTPVAE_PSTEP(QN, VN, VC, LOADNEXT)   /* gathers the next group, requests the one four behind it, adds VC's */ \
                 gather8(lds, QN, VN);                                                              \
                 LOADNEXT;                                                                          \
                 __builtin_amdgcn_sched_barrier(0);                                                 \
-                _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += VC[e];
+                CTPVAE_PADD(VC)
 #define CTPVAE_FWD_WALK_U16                                                                        \
-            vec_t vt[8];                                                                           \
-            for (int n = 0;; n += 4) {                                                             \
-                CTPVAE_PSTEP(n + 1, q1, vb, va, q1 = p[st])                 /* adds group n */     \
-                CTPVAE_PSTEP(n + 2, q2, va, vb, q2 = p[2 * st])             /* group n + 1 */      \
-                CTPVAE_PSTEP(n + 3, q3, vb, va, q3 = p[3 * st])             /* group n + 2 */      \
-                CTPVAE_PSTEP(n + 4, q0, va, vb, (p += 4 * st, q0 = p[0]))   /* group n + 3 */      \
+            int n = 0;                                                                             \
+            for (; n + 4 < ng; n += 4) {   /* group n + 4 exists: every gather below is of a live group */ \
+                CTPVAE_PSTEP(q1, vb, va, q1 = p[st])                        /* adds group n */     \
+                CTPVAE_PSTEP(q2, va, vb, q2 = p[2 * st])                    /* group n + 1 */      \
+                CTPVAE_PSTEP(q3, vb, va, q3 = p[3 * st])                    /* group n + 2 */      \
+                CTPVAE_PSTEP(q0, va, vb, (p += 4 * st, q0 = p[0]))          /* group n + 3 */      \
             }                                                                                      \
-            _Pragma("unroll") for (int e = 0; e < 8; ++e) acc += vt[e];
+            if (n + 1 >= ng) {   /* one to four groups are left, group n is in va; no index loads behind the last trip */ \
+                CTPVAE_PADD(va)                                                                    \
+            } else {                                                                               \
+                CTPVAE_PSTEP(q1, vb, va, (void)0)                                                  \
+                if (n + 2 >= ng) {                                                                 \
+                    CTPVAE_PADD(vb)                                                                \
+                } else {                                                                           \
+                    CTPVAE_PSTEP(q2, va, vb, (void)0)                                              \
+                    if (n + 3 >= ng) {                                                             \
+                        CTPVAE_PADD(va)                                                            \
+                    } else {                                                                       \
+                        CTPVAE_PSTEP(q3, vb, va, (void)0)                                          \
+                        CTPVAE_PADD(vb)                                                            \
+                    }                                                                              \
+                }                                                                                  \
+            }
 template <int NS, bool EPI, bool SEL>
 __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel(const float *__restrict__ img, PlanGeom g, FwdLayout L,
                                                                   const char *__restrict__ plan, int wgs_per_slice,
@@ -598,37 +615,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel(const float *_
             vec_t va[8], vb[8];
             gather8(lds, q0, va);
             q0 = p[0];
-            if constexpr (EPI) {   // (the epilogue variants have no registers for the form below: they keep round 3's loop)
-                for (int n = 0;; n += 4) {
-                    gather8(lds, q1, vb);
-                    q1 = p[st];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc += va[e];          // group n
-                    if (n + 1 >= ng) break;
-                    gather8(lds, q2, va);
-                    q2 = p[2 * st];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc += vb[e];          // group n + 1
-                    if (n + 2 >= ng) break;
-                    gather8(lds, q3, vb);
-                    q3 = p[3 * st];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc += va[e];          // group n + 2
-                    if (n + 3 >= ng) break;
-                    gather8(lds, q0, va);
-                    p += 4 * st;
-                    q0 = p[0];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) acc += vb[e];          // group n + 3
-                    if (n + 4 >= ng) break;
-                }
-            } else {
-                CTPVAE_FWD_WALK_U16
-            }
+            CTPVAE_FWD_WALK_U16   // (the epilogue variants too: the walk keeps no copy of the last group, so they have the registers)
         }
         if ((unsigned)cur.j < (unsigned)g.PW) {
             auto store = [&](int n, float v) {
@@ -775,6 +762,7 @@ __global__ __launch_bounds__(1024) void rotate_fwd_planned_kernel_few(const floa
 }
 #undef CTPVAE_FWD_WALK_U16
 #undef CTPVAE_PSTEP
+#undef CTPVAE_PADD
 
 // four byte taps of one dword -> four LDS byte offsets inside a cotangent row (SDWA: select a byte, shift by
 // log2(bytes per cell): 2, or 3 when two slices are interleaved as float2)
