@@ -119,8 +119,8 @@ class Model:
         above = np.cumsum(O[:, ::-1], axis=1, dtype=dtype)[:, ::-1][:, 1:]
         return ((np.log(O[:, :-1]) - np.log(above)) + np.log(np.arange(self.K - 1, 0, -1).astype(dtype))).astype(dtype)
 
-    def target(self, x):
-        """(T [C], dT/dx [C][K-1], O [C][K]) in x's dtype."""
+    def target(self, x, with_w=False):
+        """(T [C], dT/dx [C][K-1], O [C][K]) in x's dtype; with_w: and w [C][K] = O dT/dO, 0 where the clamp binds."""
         dt, K = x.dtype.type, self.K
         b = self.bijector(x)
         with np.errstate(all="ignore"):
@@ -142,7 +142,7 @@ class Model:
             fldj = ((b["lz"] + b["l1mz"]) + b["logr"][:, :-1]).sum(-1, dtype=dt)
             T = (prior + lp.astype(dt).sum((1, 2), dtype=dt)) + fldj
         assert T.dtype == dt and grad.dtype == dt
-        return T, grad, b["O"]
+        return (T, grad, b["O"], w) if with_w else (T, grad, b["O"])
 
 
 LOG_TARGET = np.float32(np.log(0.75))
@@ -190,13 +190,16 @@ def run(model, x, eps, chain_ids, seed, n_steps, L, num_adaptation_steps=0, t0=0
 
 
 # ---- the tests' problems and their acceptance rule ---------------------------------------------------------------
-SHAPES = {"toy": (2, 2), "n3": (3, 5), "n5": (5, 7), "n8": (8, 20)}     # name -> (N, A)
-SEEDS = {"toy": 11, "n3": 12, "n5": 13, "n8": 14}                       # chosen so that twin32 against twin64 stays under the caps
+# name -> (N, A).  n4, n6, n7: K - 1 = 15 ends the active lanes exactly on a 16-lane DPP row; K = 36 and 49 end them inside rows 2
+# and 3, where the scans' row_bcast:15 / row_bcast:31 steps decide the result.
+SHAPES = {"toy": (2, 2), "n3": (3, 5), "n5": (5, 7), "n8": (8, 20), "n4": (4, 16), "n6": (6, 11), "n7": (7, 9)}
+# chosen so that twin32 against twin64 stays under the caps
+SEEDS = {"toy": 11, "n3": 12, "n5": 13, "n8": 14, "n4": 16, "n6": 17, "n7": 18}
 # Step sizes of the comparisons: the toy's is the reference's 6.5e-2.  On the larger objects (a sharper posterior: more rays at
 # pnm = 1e3) that size makes the leapfrog integrator diverge from the random starts (log accept ratios down to -4e5, 67 % of the
 # chains of n5 left out after 20 steps in twin32 against twin64 alone): a bar taken from the largest value then says nothing.
 # 1e-2 keeps the trajectories stable (|lar| < 300, acceptance 40-75 %), which is where a sampler is used.
-STEP = {"toy": 6.5e-2, "n3": 1e-2, "n5": 1e-2, "n8": 1e-2}
+STEP = {"toy": 6.5e-2, "n3": 1e-2, "n5": 1e-2, "n8": 1e-2, "n4": 1e-2, "n6": 1e-2, "n7": 1e-2}
 # The documented extremes at once, outside SHAPES (the issue's cases): 8 x 8 pixels, 256 angles (32 passes over the sinogram, the
 # largest LDS request), 4 mixture components, and 32 leapfrog steps per transition.
 EXTREME = {"max": (8, 256)}
@@ -282,3 +285,88 @@ def twin_runs(oracle, name, C, n_steps, seed, L=5):
     eps = np.full(C, STEP[name], np.float32)
     runs = [run(model, model.inverse(starts, dt), eps, np.arange(C), seed, n_steps, L) for dt in (np.float32, np.float64)]
     return pb, starts, runs[0], runs[1]
+
+
+# ---- the evaluator alone: T and dT/dx of the chain state that ctpvae_hmc_init_f32 stores ---------------------------
+TIE_ANGLES = np.array([0.0, np.pi / 4, np.pi / 2, 3 * np.pi / 4, np.pi, -np.pi / 2, 0.3, 1.1])
+TARGET_PNM = 1e3
+BAND = (1e-39, 1e-37)      # O around FLT_MIN = 1.18e-38: float32 and float64 may decide the clamp differently there
+
+
+def target_cases():
+    """(N, A, M, seed): every N; one angle, a few, more than the tie angles, and ceil(64 / N) angles -- A N = 64 exactly (one full
+    pass: N = 2, 4, 8) or 65 .. 70 (a second pass with 1 .. 6 live entries: N = 5, 3, 6, 7); every M = 1 .. 4 occurs."""
+    for N in range(2, 9):
+        for A in sorted({1, 3, 11, -(-64 // N)}):
+            yield N, A, 1 + (N + A) % 4, 100 * N + A
+
+
+def target_case(oracle, N, A, M, seed, C=64):
+    """(model, theta, mask [1][A], meas [1][A][N], prior, starts [C][K]).  The angles include the rounding ties of the tap tables
+    (multiples of pi / 4); chains 0 .. C/2 - 1 start with one denormal pixel (1e-44 .. 1e-40, far below FLT_MIN, where the clamp
+    O' = max(O, FLT_MIN) binds), chains C/2 .. C - 1 inside the simplex."""
+    K = N * N
+    rng = np.random.default_rng(seed)
+    theta = np.resize(TIE_ANGLES, A).astype(np.float32)
+    obj = rng.dirichlet(np.full(K, 2.0)).astype(np.float32).reshape(1, N, N)
+    sino = oracle.rotate_fwd(obj, oracle.Geometry(N, N, False), oracle.rotate_transforms(theta, N, N))
+    mask = np.where(np.arange(A) % 2 == 0, 1.0, 0.5).astype(np.float32)[None]
+    if A > 2:
+        mask[0, 1] = 0.0
+    meas = oracle.poisson_measure(sino, mask, TARGET_PNM, 5)
+    prior = (np.full(M, 1.0 / M), rng.uniform(0.5, 2.0, (M, K)))
+    starts = rng.dirichlet(np.full(K, 3.0), C).astype(np.float32)
+    for c in range(C // 2):
+        starts[c, rng.integers(K)] = np.float32(10.0 ** -rng.uniform(40, 44))
+    model = Model(oracle, theta, N, mask, meas, TARGET_PNM, *prior, chains_per_object=C)
+    return model, theta, mask, meas, prior, starts
+
+
+def _chain_bar(v32, v64):
+    """bar()'s rule per chain: max(1e-5 max_k |v64[c]|, 8 max_k |v32[c] - v64[c]|), [C]."""
+    v32, v64 = np.asarray(v32, np.float64).reshape(len(v64), -1), np.asarray(v64, np.float64).reshape(len(v64), -1)
+    with np.errstate(invalid="ignore"):
+        return np.maximum(1e-5 * np.abs(v64).max(-1), 8.0 * np.abs(v32 - v64).max(-1))
+
+
+def check_target(model, starts, x_dev, g_dev=None, T_dev=None):
+    """The evaluator at the device's own point: x_dev [C][K-1] float32 (the device's inverse bijector of `starts`), g_dev [C][K-1]
+    and T_dev [C] what it stored for it.  Reference: Model.target(x_dev) in float64; bars: bar()'s factor 8 over the float32
+    restatement and its 1e-5 floor, PER CHAIN (boundary and interior chains differ by orders of magnitude).  x_dev itself is held
+    to Model.inverse(starts) on every chain in the same way.  A chain is left out of the T and dT/dx comparison when the float32
+    restatement is not finite there, when max |g64| >= 1e30 (a ray whose only taps are bound pixels: the float32 formula itself
+    overflows, in the reference too), or when some O64 lies in BAND.  T alone, which does not overflow there (log of FLT_MIN pnm
+    is finite), is ALSO compared on the left-out chains whose float32 T is finite and that are outside BAND: those are the only
+    chains on which the VALUE the clamp puts into the projection shows (elsewhere a bound pixel shares every ray with larger
+    ones).  Returns (chains left out, compared chains with a bound pixel, chains in BAND, worst error / bar per quantity); asserts
+    when g_dev and T_dev are given."""
+    x_dev = np.asarray(x_dev)
+    assert x_dev.dtype == np.float32
+    with np.errstate(all="ignore"):
+        T64, g64, O64 = model.target(x_dev.astype(np.float64))
+        T32, g32, _ = model.target(x_dev)
+        if starts is None:                                                                      # the default start: x = 0
+            x64, x32 = np.zeros(x_dev.shape), np.zeros(x_dev.shape, np.float32)
+        else:
+            x64, x32 = model.inverse(starts, np.float64), model.inverse(starts, np.float32)
+        band = ((O64 >= BAND[0]) & (O64 <= BAND[1])).any(-1)
+        out = ~(np.isfinite(g32).all(-1) & np.isfinite(T32)) | ~(np.abs(g64).max(-1) < 1e30) | band
+    keep = ~out
+    keep_T = keep | (np.isfinite(T32) & ~band)
+    bound = int(((O64 < TINY).any(-1) & keep).sum())
+    worst = dict(x=0.0, g=0.0, T=0.0)
+    if g_dev is not None:
+        with np.errstate(all="ignore"):
+            b_x, b_g, b_T = _chain_bar(x32, x64), _chain_bar(g32, g64), _chain_bar(T32, T64)
+            e_x = np.abs(x_dev.astype(np.float64) - x64).max(-1)
+            e_g = np.abs(np.asarray(g_dev, np.float64) - g64).max(-1)
+            e_T = np.abs(np.asarray(T_dev, np.float64) - T64)
+        for name, e, b, sel in (("x", e_x, b_x, np.ones_like(keep)), ("g", e_g, b_g, keep), ("T", e_T, b_T, keep_T)):
+            if sel.any():
+                with np.errstate(all="ignore"):
+                    ratio = np.where(e[sel] == 0.0, 0.0, e[sel] / b[sel])
+                bad = ~(e[sel] <= b[sel])                                                      # (a NaN fails)
+                worst[name] = float(ratio.max())
+                c = int(np.flatnonzero(sel)[np.argmax(bad)])
+                assert not bad.any(), (name, "chain", c, float(e[c]), float(b[c]), int(bad.sum()))
+    return int(out.sum()), bound, int(band.sum()), worst

@@ -61,6 +61,8 @@ def test_twenty_transitions_against_the_twin(name):
     Seen on the MI355X (fraction left out; worst error / bar for log_accept_ratio, sample, target_log_prob):
       1 step:   toy 0, 0.16 / 0.03 / 0.03;  n3 0, 0.14 / 0.02 / 0.03;  n5 0, 0.06 / 0.04 / 0.03;  n8 0.004, 0.09 / 0.04 / 0.03
       20 steps: toy 0, 0.33 / 0.34 / 0.19;  n3 0.016, 0.27 / 0.02 / 0.03;  n5 0.016, 0.13 / 0.06 / 0.03;  n8 0.008, 0.22 / 0.06 / 0.03
+      1 step:   n4 0, 0.14 / 0.02 / 0.02;  n6 0, 0.12 / 0.03 / 0.02;  n7 0, 0.06 / 0.05 / 0.03
+      20 steps: n4 0.008, 0.23 / 0.03 / 0.02;  n6 0.012, 0.14 / 0.05 / 0.03;  n7 0.023, 0.14 / 0.07 / 0.03
     -- the device sits well inside the factor 8 (its error is about that of the float32 restatement itself)."""
     _against_twin(name, 20, 0.20)
 
