@@ -174,6 +174,16 @@ SIGNATURES = {
     "ctpvae_periodic_pad_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ctpvae_maxout_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),
     "ctpvae_maxout_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp]),
+    "ctpvae_dropout_fwd_f32": (_c_int, [_vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                        ctypes.c_uint, _c_float, _vp, _vp]),
+    "ctpvae_dropout_bwd_f32": (_c_int, [_vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                        ctypes.c_uint, _c_float, _vp, _vp]),
+    "ctpvae_dropout_pad_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_longlong,
+                                            ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, _c_float, _vp, _vp]),
+    "ctpvae_dropout_pad_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_longlong,
+                                            ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, _c_float, _vp, _vp]),
+    "ctpvae_dropout_keep_host_u8": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                             ctypes.c_uint, _vp]),
     "ctpvae_merit_tile": (_c_int, []),
     "ctpvae_merit_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "ctpvae_merit_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),

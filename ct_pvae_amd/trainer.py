@@ -32,8 +32,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import dataset_io, phantoms, sharding
-from .convblock import maxout, periodic_pad
+from . import convblock, dataset_io, phantoms, sharding
+from .convblock import dropout, dropout_pad, maxout, periodic_pad
 from .create_masks import create_all_masks
 from .fbp import iradon_all
 from .forward_functions import num_proj_pix
@@ -109,15 +109,39 @@ class _PeriodicPad(torch.autograd.Function):
         return gw.new_zeros(gw.shape[:2] + (H, W)).index_add_(2, ctx.ih, gw), None
 
 
+class DropoutKey:
+    """What the ConvBlocks of ONE network share of their dropout (--dp): the rate and the seed for good, the draw (the step index) and
+    first_object (the offset of the network's batch in the global one) per call -- set(draw, first_object) before a training pass,
+    clear() after it.  While no draw is set the blocks do not drop, in train() as in eval(): the evaluations run the networks as the
+    reference's training=False does.  Not a module: dropout has no parameters and no state_dict entry."""
+
+    def __init__(self, rate, seed):
+        self.rate, self.seed = float(rate), int(seed)
+        self.draw, self.first_object = None, 0
+        convblock._rate_args("DropoutKey", self.rate)        # a bad rate is refused here, not at the first step
+
+    def set(self, draw, first_object=0):
+        self.draw, self.first_object = int(draw), int(first_object)
+        return self
+
+    def clear(self):
+        self.draw = None
+
+
 class ConvBlock(nn.Module):
-    """Conv2D => maxout of two convolutions (ctvae/models.py:267-342); 'periodic' padding for the strided/plain
+    """Dropout => Conv2D => maxout of two convolutions (ctvae/models.py:267-342); 'periodic' padding for the strided/plain
     convolutions (:219-263), Conv2DTranspose(padding='same') for up-sampling.  fused_blocks: the padding and the maxout are one launch
     each way (convblock.periodic_pad / maxout, csrc/convblock.hip) instead of _PeriodicPad's and _Maxout's chains of torch launches;
-    the parameters and their names are the same either way."""
+    the parameters and their names are the same either way.  dropout: None, or the network's DropoutKey; `layer` is then the block's
+    number in the stream.  In training mode, while the key holds a draw, the block drops its input (:283-284) -- inside the pad's launch
+    with fused_blocks (convblock.dropout_pad), as convblock.dropout in front of _PeriodicPad without, and in front of the transposed
+    convolution, which has no pad, either way.  The mask is a function of (seed, draw, layer, global object, element): no generator
+    state, nothing stored for the backward."""
 
-    def __init__(self, cin, cout, k, stride, transpose, fused_blocks=False):
+    def __init__(self, cin, cout, k, stride, transpose, fused_blocks=False, dropout=None, layer=0):
         super().__init__()
         self.k, self.stride, self.transpose, self.fused_blocks = k, stride, transpose, bool(fused_blocks)
+        self.dropout, self.layer = dropout, int(layer)
         # the two convolutions of the maxout are ONE convolution with 2 * cout output channels (half the launches);
         # each half is initialised as its own GlorotUniform layer
         if transpose:
@@ -136,30 +160,44 @@ class ConvBlock(nn.Module):
         nn.init.zeros_(self.ab.bias)
 
     def forward(self, x):
-        if not self.transpose:
+        d = self.dropout if self.training and self.dropout is not None and self.dropout.draw is not None else None
+        key = dict(seed=d.seed, draw=d.draw, layer=self.layer, first_object=d.first_object) if d is not None else None
+        if self.transpose:
+            if d is not None:
+                x = dropout(x.contiguous(), d.rate, **key)
+        else:
             pads = []
             for n in (x.shape[-1], x.shape[-2]):   # last axis first, as torch.nn.functional.pad orders them
                 p = self.k - (n % self.stride if n % self.stride else self.stride)
                 pads += [p // 2 + p % 2, p // 2]
-            x = periodic_pad(x.contiguous(), tuple(pads)) if self.fused_blocks else _PeriodicPad.apply(x, tuple(pads))
+            if d is None:
+                x = periodic_pad(x.contiguous(), tuple(pads)) if self.fused_blocks else _PeriodicPad.apply(x, tuple(pads))
+            elif self.fused_blocks:
+                x = dropout_pad(x.contiguous(), tuple(pads), d.rate, **key)
+            else:
+                x = _PeriodicPad.apply(dropout(x.contiguous(), d.rate, **key), tuple(pads))
         return maxout(self.ab(x).contiguous()) if self.fused_blocks else _Maxout.apply(self.ab(x))
 
 
 class EncodeNet(nn.Module):
     """create_encode_net, ctvae/models.py:23-108: returns the list of skips (the first one is the repeated input)."""
 
-    def __init__(self, cin, feature_maps, fmm, kernel, stride, inter_layers, inter_kernel, fused_blocks=False):
+    def __init__(self, cin, feature_maps, fmm, kernel, stride, inter_layers, inter_kernel, fused_blocks=False, dropout=None, first_layer=0):
         super().__init__()
         self.fmm = fmm
         c = cin * fmm
         self.channels = [c]
         self.blocks = nn.ModuleList()
+        self.dropout = dropout
+        layer = iter(range(first_layer, 2 ** 24))            # the blocks' dropout layers: numbered in construction order
         for f in feature_maps:
-            layers = [ConvBlock(c, c, inter_kernel, 1, False, fused_blocks=fused_blocks) for _ in range(inter_layers)]
-            layers.append(ConvBlock(c, f * fmm, kernel, stride, False, fused_blocks=fused_blocks))
+            layers = [ConvBlock(c, c, inter_kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer))
+                      for _ in range(inter_layers)]
+            layers.append(ConvBlock(c, f * fmm, kernel, stride, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer)))
             self.blocks.append(nn.Sequential(*layers))
             c = f * fmm
             self.channels.append(c)
+        self.num_layers = next(layer) - first_layer
 
     def forward(self, x):
         x = x.repeat_interleave(self.fmm, dim=1)   # tf.repeat(output, feature_maps_multiplier, axis=-1)
@@ -173,18 +211,22 @@ class EncodeNet(nn.Module):
 class DecodeNet(nn.Module):
     """create_decode_net, ctvae/models.py:112-215 (the code concatenates every skip, including the input level)."""
 
-    def __init__(self, enc_channels, fmm, out_channels, kernel, stride, inter_layers, inter_kernel, fused_blocks=False):
+    def __init__(self, enc_channels, fmm, out_channels, kernel, stride, inter_layers, inter_kernel, fused_blocks=False, dropout=None,
+                 first_layer=0):
         super().__init__()
         lat = [c // fmm for c in enc_channels]     # channels of the sampled latents
         self.ups = nn.ModuleList()
+        self.dropout = dropout
+        layer = iter(range(first_layer, 2 ** 24))            # as the encoder's; the trainer numbers the decoder's blocks after them
         c = lat[-1]
         for lvl in range(len(enc_channels) - 2, -1, -1):
-            layers = [ConvBlock(c, enc_channels[lvl], kernel, stride, True, fused_blocks=fused_blocks)]
-            layers += [ConvBlock(enc_channels[lvl], enc_channels[lvl], inter_kernel, 1, False, fused_blocks=fused_blocks)
-                       for _ in range(inter_layers)]
+            layers = [ConvBlock(c, enc_channels[lvl], kernel, stride, True, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer))]
+            layers += [ConvBlock(enc_channels[lvl], enc_channels[lvl], inter_kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout,
+                                 layer=next(layer)) for _ in range(inter_layers)]
             self.ups.append(nn.Sequential(*layers))
             c = enc_channels[lvl] + lat[lvl]
-        self.head = ConvBlock(c, 2 * out_channels, kernel, 1, False, fused_blocks=fused_blocks)
+        self.head = ConvBlock(c, 2 * out_channels, kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer))
+        self.num_layers = next(layer) - first_layer
 
     def forward(self, latents):
         x = latents[-1]
@@ -370,8 +412,15 @@ class PVAETrainer:
         fm = [int(a.nfm * a.nfmm ** i) for i in range(a.num_blocks)]
         fmm = 1 if a.deterministic else 2
         fused_blocks = bool(getattr(a, "fused_blocks", False))
-        self.enc = EncodeNet(len(a.algorithms) + 1, fm, fmm, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks).to(device)
-        self.dec = DecodeNet(self.enc.channels, fmm, 1, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks).to(device)
+        # --dp: one DropoutKey per network (their batches differ: B objects in the encoder, ns * B sample-major in the decoder); the
+        # blocks' layers run through the encoder, then the decoder.  With --dp 0 the networks are built exactly as without the flag.
+        dp = float(getattr(a, "dropout_prob", 0.0) or 0.0)
+        self.enc_drop = DropoutKey(dp, a.head_seed) if dp > 0 else None
+        self.dec_drop = DropoutKey(dp, a.head_seed) if dp > 0 else None
+        self.enc = EncodeNet(len(a.algorithms) + 1, fm, fmm, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks,
+                             dropout=self.enc_drop).to(device)
+        self.dec = DecodeNet(self.enc.channels, fmm, 1, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks,
+                             dropout=self.dec_drop, first_layer=self.enc.num_layers).to(device)
         if self.world > 1:   # identical initial weights on every rank
             for p in list(self.enc.parameters()) + list(self.dec.parameters()):
                 torch.distributed.broadcast(p.data, 0)
@@ -477,12 +526,23 @@ class PVAETrainer:
         fused_lat = None
         if getattr(a, "fused_latents", False):
             fused_lat = (a.head_seed, self.iter, sharding.shard_range(a.batch_size, self.rank, self.world)[0])   # _batch's lo
-        loss_vec, kl, loglik, _ = find_loss_vae_unsup(proj_sample, mask, input_encode, self.enc, self.dec, pnm_i,
-                                                      self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
-                                                      theta=self.theta_host, angles_i=angles_i, pad=self.pad,
-                                                      deterministic=a.deterministic, use_normal=a.use_normal,
-                                                      model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
-                                                      fused_head=fused, fused_latents=fused_lat)
+        # --dp: seed = --head_seed, draw = the step index; the objects are counted as the head counts them (rank * B in the encoder,
+        # rank * ns * B in the decoder's sample-major batch), so a run replays at its own world size.  The keys hold a draw only while
+        # the training pass is built: every other caller of the networks (the evaluations, --pixel_dist) runs them without dropout.
+        if self.enc_drop is not None:
+            nb = input_encode.shape[0]
+            self.enc_drop.set(self.iter, self.rank * nb)
+            self.dec_drop.set(self.iter, self.rank * (1 if a.deterministic else a.ns) * nb)
+        try:
+            loss_vec, kl, loglik, _ = find_loss_vae_unsup(proj_sample, mask, input_encode, self.enc, self.dec, pnm_i,
+                                                          self.sqrt_reg, kl_anneal, a.klm, num_samples=a.ns,
+                                                          theta=self.theta_host, angles_i=angles_i, pad=self.pad,
+                                                          deterministic=a.deterministic, use_normal=a.use_normal,
+                                                          model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
+                                                          fused_head=fused, fused_latents=fused_lat)
+        finally:
+            if self.enc_drop is not None:
+                self.enc_drop.clear(), self.dec_drop.clear()
         # ctvae/main_ct_vae.py:478 reduce_mean(loss_M_VAE) / 1e5 = mean_b(KL term) - loglik, where loglik already sums
         # over the batch.  Written so that the ranks' losses ADD UP to the global one (gradients are summed over ranks):
         # each rank contributes its objects' KL / global_B and its own objects' log-likelihood.
@@ -676,6 +736,13 @@ class PVAETrainer:
         return m
 
 
+def _dropout_prob(text):
+    p = float(text)
+    if not 0.0 <= p < 1.0 or (p > 0.0 and not 0.0 < float(np.float32(p)) < 1.0):
+        raise argparse.ArgumentTypeError(f"--dp must satisfy 0 <= p < 1, in float32 too (got {text})")
+    return p
+
+
 def get_args(argv=None):
     """The reference's flags that reach the path (ctvae/main_ct_vae.py:30-116), same spellings and defaults."""
     p = argparse.ArgumentParser(description="P-VAE training with the MI355X projector")
@@ -721,6 +788,13 @@ def get_args(argv=None):
                         "two copies of a pixel per axis, the same values; independent of --normal and --det.  Measured at the c3 recipe "
                         "(profiles/convblock_timing.txt): alone NOT measurably faster (173.8 against 173.1 steps/s, the windows overlap); "
                         "with --fused_head --fused_latents 248.1 against 237.6 steps/s, the windows overlap too")
+    p.add_argument("--dp", type=_dropout_prob, dest="dropout_prob", default=0.0,
+                   help="dropout probability of every ConvBlock's input (ctvae/main_ct_vae.py:41-42, ctvae/models.py:283-284), 0 <= p < 1; "
+                        "0 (the default): no dropout, the networks and their launches as without the flag.  The masks are Philox-keyed by "
+                        "(--head_seed, step index, block, object, element) (csrc/convblock.hip), not drawn from torch's global generator, "
+                        "and drawn again in the backward instead of stored; with --fused_blocks they ride the pad's launches.  Training "
+                        "steps only: the final evaluation, --pixel_dist and --final_merit run the networks without dropout")
+    p.add_argument("--ufs", action="store_true", help="accepted and ignored: the reference parses it (use_first_skip) and never reads it")
     p.add_argument("--reproducible", action="store_true",
                    help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
                         "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")

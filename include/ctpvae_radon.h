@@ -782,6 +782,40 @@ int ctpvae_periodic_pad_bwd_f32(const float *g_dev, int planes, int H, int W, in
 int ctpvae_maxout_fwd_f32(const float *y_dev, int n, int len, float *out_dev, unsigned char *first_out_dev, ctpvae_stream_t stream);
 int ctpvae_maxout_bwd_f32(const float *g_dev, const unsigned char *first_dev, int n, int len, float *gy_out_dev, ctpvae_stream_t stream);
 
+/* ---- the ConvBlock's dropout (ctvae/models.py:58-61, :141-144, :283-284: on the block's input, before the padding), alone and inside
+ * the periodic pad's launches; all five added at ABI 3400 (csrc/convblock.hip states the layout).  The stream is part of the
+ * definition: Philox4x32-10, key = seed.  The block input is [n][len] (len = C * H * W); element i of object b has the 64-bit flat
+ * index e = (first_object + b) * len + i and takes word w = e & 3 of the block with counter (lo32(e >> 2), hi32(e >> 2), draw,
+ * 0x44000000 | layer), layer < 2^24 (the top byte 0x44 keeps the fourth counter word apart from the latents' 0x4C......, the head's
+ * 0x544E48, the HMC sampler's 0x484D43 and the Poisson sampler's 0).
+ *   keep   k = w >> 8, u = k * 2^-24 (exact in float32); keep iff u >= float32(rate), i.e. k >= T with T = ceil(float32(rate) * 2^24),
+ *          which the HOST computes and passes: 1 <= T <= 2^24 - 1 for 0 < float32(rate) < 1
+ *   value  keep ? x * scale : +0.0f, scale = float32(1 / (1 - rate)) computed in double by the host (1 <= scale <= 2^24): one float32
+ *          multiply.  A dropped element is a selection, not a product with 0: a dropped inf or NaN gives +0, where TensorFlow's
+ *          x * scale * mask gives NaN (the maxout's backward selects the same way).
+ *   _dropout_fwd_f32: out_dev [n][len] of x_dev [n][len].
+ *   _dropout_bwd_f32: gx_out_dev [n][len] = keep ? scale * g : +0.0f of the cotangent g_dev [n][len].
+ *   _dropout_pad_fwd_f32: out_dev [n * channels][OH][OW], out[p][r][q] = drop(x)[p][(r - hl) mod H][(q - wl) mod W], len = channels * H * W:
+ *     the decision belongs to the SOURCE element, every wrapped copy of it shares it; the bits of _periodic_pad_fwd_f32 of _dropout_fwd_f32.
+ *   _dropout_pad_bwd_f32: gx_out_dev [n * channels][H][W] = keep ? scale * acc : +0.0f, acc the two ascending folds of
+ *     _periodic_pad_bwd_f32 in their order.
+ *   The backwards draw the mask again from the same (first_object, seed, draw, layer, T): the forwards keep nothing for them.
+ *   _dropout_keep_host_u8: the keep decisions (1 = kept) of the same arguments into HOST memory out_host [n][len]; needs no GPU.
+ * A batch cut into calls with first_object drops what the whole batch drops.  Every extent >= 1, every pad >= 0, the element counts of
+ * the device calls (n * len, n * channels * OH * OW) <= 2^31 - 1, first_object >= 0 and (first_object + n) * len <= 2^63 - 1. */
+int ctpvae_dropout_fwd_f32(const float *x_dev, int n, int len, long long first_object, unsigned long long seed, unsigned draw, unsigned layer,
+                           unsigned T, float scale, float *out_dev, ctpvae_stream_t stream);
+int ctpvae_dropout_bwd_f32(const float *g_dev, int n, int len, long long first_object, unsigned long long seed, unsigned draw, unsigned layer,
+                           unsigned T, float scale, float *gx_out_dev, ctpvae_stream_t stream);
+int ctpvae_dropout_pad_fwd_f32(const float *x_dev, int n, int channels, int H, int W, int wl, int wr, int hl, int hr, long long first_object,
+                               unsigned long long seed, unsigned draw, unsigned layer, unsigned T, float scale, float *out_dev,
+                               ctpvae_stream_t stream);
+int ctpvae_dropout_pad_bwd_f32(const float *g_dev, int n, int channels, int H, int W, int wl, int wr, int hl, int hr, long long first_object,
+                               unsigned long long seed, unsigned draw, unsigned layer, unsigned T, float scale, float *gx_out_dev,
+                               ctpvae_stream_t stream);
+int ctpvae_dropout_keep_host_u8(int n, int len, long long first_object, unsigned long long seed, unsigned draw, unsigned layer, unsigned T,
+                                unsigned char *out_host);
+
 /* ---- (MSE, SSIM, PSNR) of a batch of image pairs in float64 (the reference's compare, ctvae/helper_functions.py:394-418, with
  * scikit-image 0.18's structural_similarity: uniform window, K1 0.01, K2 0.03, sample covariance, the data range taken from the
  * reference image); added at ABI 3400.  ref_dev, test_dev [n][X][Y] contiguous, both float (_f32; widened to double first) or both
