@@ -7,7 +7,7 @@ template <int PPT, int MAXT, int NS, int DUP = 1, bool SHORT = false>
 __global__ __launch_bounds__(MAXT) void CTPVAE_BWD_PLANNED_KERNEL(const float *__restrict__ gsino, PlanGeom g, BwdLayout L,
                                                                  const uint4 *__restrict__ idx, int tiles_y, int g_S,
                                                                  SliceScale scale, float *__restrict__ gimg, unsigned inv_tiles,
-                                                                 unsigned inv_nxb, unsigned stage_magic)
+                                                                 unsigned inv_nxb, unsigned stage_magic, unsigned idx_req)
 {
     static_assert(!SHORT || DUP == 1, "SHORT launches are tf_compat plans of at most 32 angles");
     typedef typename SliceVec<NS>::type vec_t;
@@ -66,6 +66,13 @@ __global__ __launch_bounds__(MAXT) void CTPVAE_BWD_PLANNED_KERNEL(const float *_
     // every wave of a many-angle launch waited out an L2 round trip per group -- SQ_WAIT_ANY was 46 % of the wave cycles at
     // B = 50 x 180 angles with the LDS array 22 % busy -- and all sixteen waves of the CU's one workgroup did so together.
     uint4 q[2][PPT];
+    // (SHORT: the owned rows' offsets in a group, row * Wpad + column, once for every request below -- each sits in a block of its own; a
+    // request's address is the plan's, a scalar, and a 32-bit byte offset: H Wpad < 2^24 with H < 2^16, Wpad <= 256, so the plan is < 2^30 bytes)
+    [[maybe_unused]] unsigned erow[PPT];
+    if constexpr (SHORT) {
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) erow[k] = (unsigned)min(y0 + k * nwaves, g.H - 1) * (unsigned)L.Wpad + (unsigned)xcol;
+    }
     auto load_group = [&](int a16, auto slot_tag) {
         constexpr int SLOT = decltype(slot_tag)::value;
 #pragma unroll
@@ -74,16 +81,48 @@ __global__ __launch_bounds__(MAXT) void CTPVAE_BWD_PLANNED_KERNEL(const float *_
 #ifdef CTPVAE_TUNE_BWD_NOIDX
             if (a16 > 0) continue;   // timing only: every group reuses the first index vectors (no index streaming)
 #endif
-            q[SLOT][k] = SHORT ? p[(unsigned)(a16 * g.H + y) * (unsigned)L.Wpad] : p[((size_t)a16 * g.H + y) * L.Wpad];
+            if constexpr (SHORT) q[SLOT][k] = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(idx) + (((unsigned)(a16 * g.H) * (unsigned)L.Wpad + erow[k]) << 4));
+            else q[SLOT][k] = p[((size_t)a16 * g.H + y) * L.Wpad];
         }
     };
-    load_group(0, std::integral_constant<int, 0>{});       // index loads fly while the cotangent rows land
-    if constexpr (!SHORT) load_group(min(1, L.NA16 - 1), std::integral_constant<int, 1>{});
+    // SHORT: the launch's LAST index vector (q2nd), of which the gathers read the first 1 .. 4 dwords, comes either whole -- the uint4 of
+    // the second group, which IS the first when there is one -- or from the plan's compact tail section, which holds exactly the dwords
+    // that are read as records of 1 .. 3 dwords per (row, padded column) behind the uint4 array (NA16 H Wpad vectors: a multiple of
+    // 1 KB): one load of that many dwords per owned row, a wave's 64 records one contiguous run (byte offsets < 12 H Wpad < 2^32); the
+    // other components of q2nd are then never read.  Which requests the launch makes is a launch constant, idx_req (launch_bwd_planned
+    // derives it from the same A as the gathers' cases below), one BIT per request: to the compiler five independent jumps over a short
+    // block each -- from equality tests of a record size it builds a switch, which its structurizer flattens into twice the
+    // instructions.  The full first vector is requested last: the compiler guards the q2nd registers of one block against the loads
+    // of the blocks before it with waits, which find nothing in flight as only one of those blocks is ever run.
     [[maybe_unused]] uint4 q2nd[PPT];
-    if constexpr (SHORT) {
+    if constexpr (!SHORT) {
+        load_group(0, std::integral_constant<int, 0>{});       // index loads fly while the cotangent rows land
+        load_group(min(1, L.NA16 - 1), std::integral_constant<int, 1>{});
+    } else {
+        const char *tail = reinterpret_cast<const char *>(idx + (unsigned)(L.NA16 * g.H) * (unsigned)L.Wpad);
+        if (idx_req & kIdxReqTailWhole) {
 #pragma unroll
-        for (int k = 0; k < PPT; ++k)
-            q2nd[k] = p[(unsigned)(min(1, L.NA16 - 1) * g.H + min(y0 + k * nwaves, g.H - 1)) * (unsigned)L.Wpad];   // (its second group)
+            for (int k = 0; k < PPT; ++k)   // (its second group)
+                q2nd[k] = *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(idx) + (((unsigned)(min(1, L.NA16 - 1) * g.H) * (unsigned)L.Wpad + erow[k]) << 4));
+            asm volatile("; whole tail vectors");
+        }
+        auto tail_rows = [&](auto t_tag) {
+            constexpr int T = decltype(t_tag)::value;
+            struct Rec { unsigned w[T]; };
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const Rec r = *reinterpret_cast<const Rec *>(tail + erow[k] * (unsigned)sizeof(Rec));
+                q2nd[k].x = r.w[0];
+                if constexpr (T > 1) q2nd[k].y = r.w[1];
+                if constexpr (T > 2) q2nd[k].z = r.w[2];
+            }
+            // (a case ends in a line of its own: the compiler would otherwise share the cases' first dwords in one load behind them)
+            asm volatile("; tail records of %0 dwords" ::"n"(T));
+        };
+        if (idx_req & kIdxReqTail1) tail_rows(std::integral_constant<int, 1>{});
+        if (idx_req & kIdxReqTail2) tail_rows(std::integral_constant<int, 2>{});
+        if (idx_req & kIdxReqTail3) tail_rows(std::integral_constant<int, 3>{});
+        if (idx_req & kIdxReqFirst) load_group(0, std::integral_constant<int, 0>{});   // (records and A <= 12: the launch loads no uint4 at all)
     }
 
     const int VA = g.A * DUP;                            // virtual angles (= angles unless DUP = 2)

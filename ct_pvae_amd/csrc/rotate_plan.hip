@@ -25,6 +25,8 @@
 //                               lanes of a 32-lane group share a bank at any angle.
 // Backward plan  idx[a16][y][x]: uint4 = for angles 16*a16..16*a16+15, one BYTE each: the detector bin that
 //                               TensorFlow's gradient op reads for pixel (y, x), or 255 (a cell holding 0.0f).
+//                tail[y][x]   : (A mod 16 = 1 .. 12 only) the live dwords of the LAST group's uint4 again, t = ceil((A mod 16) / 4) = 1 .. 3
+//                               per (y, x), behind the idx array: what a launch of at most 32 angles loads in place of that uint4.
 #include <algorithm>
 #include <atomic>
 #include <climits>
@@ -77,6 +79,14 @@ static FwdLayout fwd_layout(const PlanGeom &g)
 // (== 1 mod 32): bins 0..PW-1, then zeros up to cell 256, so a dead tap reads row cell 255 = 0.0f and needs no select.
 // dup = 2: the EXACT-transpose plan -- two taps per (angle, pixel), stored as "virtual angles" 2a and 2a + 1 that both read
 // the staged cotangent row of angle a (see rotate_exact_plan_kernel)
+// Dwords of a compact tail record, 0 = the plan has no such section.  A launch of at most 32 angles gathers A mod 16 taps of its last
+// index vector; when those fill t = 1 .. 3 dwords (A mod 16 = 1 .. 12), the tf_compat plan holds them once more as records of t
+// dwords per (row y, padded column x), x fastest, so that the SHORT kernels load t dwords per owned row where the uint4 would be 4.
+static int bwd_tail_dwords(int A, int dup)
+{
+    const int r = A % 16;
+    return dup == 1 && r >= 1 && r <= 12 ? (r + 3) / 4 : 0;
+}
 static BwdLayout bwd_layout(const PlanGeom &g, int dup = 1)
 {
     BwdLayout L;
@@ -86,6 +96,9 @@ static BwdLayout bwd_layout(const PlanGeom &g, int dup = 1)
     L.pitchg = kBwdPitch;
     L.chunkA = std::min(L.NA16 * 16, kBwdChunk);
     L.bytes = (long long)L.NA16 * g.H * L.Wpad * 16;
+    // the compact tail section (tf_compat plans only), 256-byte aligned behind the uint4 array -- whose size is a multiple of 1 KB
+    // already (Wpad % 64 == 0): the SHORT kernels find the section at idx + NA16 H Wpad
+    L.bytes = (L.bytes + 255) / 256 * 256 + (long long)bwd_tail_dwords(g.A, dup) * g.H * L.Wpad * 4;
     return L;
 }
 static bool fwd_plan_fits(const PlanGeom &g)
@@ -206,7 +219,7 @@ __global__ __launch_bounds__(64) void rotate_fwd_plan_kernel(PlanGeom g, const f
 }
 
 __global__ __launch_bounds__(64) void rotate_bwd_plan_kernel(PlanGeom g, const float *__restrict__ Tinv8, BwdLayout L,
-                                                             uint4 *__restrict__ idx)
+                                                             uint4 *__restrict__ idx, int tail_t)
 {
     const int xb = blockIdx.x, yrow = blockIdx.y, a16 = blockIdx.z, lane = threadIdx.x;
     const int xcol = xb * 64 + lane;
@@ -227,6 +240,12 @@ __global__ __launch_bounds__(64) void rotate_bwd_plan_kernel(PlanGeom g, const f
         w[e >> 2] |= v << (8 * (e & 3));
     }
     idx[((size_t)a16 * g.H + yrow) * L.Wpad + xcol] = make_uint4(w[0], w[1], w[2], w[3]);
+    if (tail_t > 0 && a16 == L.NA16 - 1) {   // the compact tail section: the last group's first tail_t dwords once more (bwd_layout)
+        unsigned *rec = reinterpret_cast<unsigned *>(idx + (size_t)L.NA16 * g.H * L.Wpad) + ((size_t)yrow * L.Wpad + xcol) * tail_t;
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+            if (d < tail_t) rec[d] = w[d];
+    }
 }
 
 // Exact-transpose plan.  The forward adds img[tap(a, i, j)] into sino[a][j]; its transpose adds g[a][j] into every pixel
@@ -840,6 +859,10 @@ __device__ __forceinline__ void gather8(const float *lds, unsigned w0, unsigned 
 // waves issue on a SIMD, so a SHORT launch runs the code of the index dwords it HAS: the full vector of sixteen taps as straight-line
 // code when A > 16, then one of four straight-line cases for the 1 .. 4 dwords of its tail (gather_dwords) -- no slot that is jumped
 // over and zero-filled, no add of a zero (profiles/r15_bwd_short_gather_isa.txt, tools/count_bwd_gather_isa.py).
+// The index requests of a SHORT launch (the kernels' idx_req, one bit each): the last index vector's 1 .. 3 live dwords from the plan's
+// compact tail section, or that vector whole; the full first vector (A > 16 -- and wherever the last is read whole: the form from
+// before the section existed, knob BWD_TAIL = 0, requested both).
+constexpr unsigned kIdxReqTail1 = 1u, kIdxReqTail2 = 2u, kIdxReqTail3 = 4u, kIdxReqFirst = 8u, kIdxReqTailWhole = 16u;
 // (the kernel's text: rotate_bwd_planned_kernel.h, compiled once per store policy of the gradient image; of the write-through text only
 // the SHORT forms are launched, so only they are instantiated -- launch_bwd_planned's rule)
 #define CTPVAE_BWD_PLANNED_KERNEL rotate_bwd_planned_kernel
@@ -1043,7 +1066,7 @@ int ctpvae_rotate_plan_build_f32(const float *T8_dev, const float *Tinv8_dev, in
         CTPVAE_REQUIRE(H <= 65535, "rotate_plan_build: at most 65535 rows");
         const BwdLayout L = bwd_layout(g);
         hipLaunchKernelGGL(rotate_bwd_plan_kernel, dim3(L.nXB, H, L.NA16), dim3(64), 0, (hipStream_t)stream, g, Tinv8_dev, L,
-                           (uint4 *)bwd_plan_dev);
+                           (uint4 *)bwd_plan_dev, bwd_tail_dwords(A, 1));
         CTPVAE_LAUNCH_CHECK("rotate_bwd_plan_kernel");
     }
     return CTPVAE_OK;
@@ -1464,6 +1487,15 @@ static int launch_bwd_planned(const float *gsino_dev, int S, int H, int W, int P
                 waves = w_more;
         }
     }
+    // At most 32 angles, re-derived on the kernels that read the compact tail (tools/sweep_bwd_waves.py at 20 and 32 angles,
+    // profiles/r17_bwd_tail_rules.txt): 22-row tiles of ELEVEN waves where they save the 16-row tiles a round of workgroups and fill
+    // the one or two rounds they need to 15/16 -- 128 x 128: 40 slices, 240 workgroups for 320, and 80 slices, 480 for 640.  Elsewhere
+    // the heights were level within the sweep's scatter (50 slices: 13 waves 3.83 us, 8 waves 3.89) or lost, and the rule stands.
+    if (dup == 1 && A <= 32 && ns == 2 && S > 16) {
+        auto wgs = [&](int w) { return (long long)units * L.nXB * ceil_div(H, w * ppt); };
+        const long long r8 = (wgs(8) + 255) / 256, r11 = (wgs(11) + 255) / 256;
+        if (r11 < r8 && r11 <= 2 && wgs(11) * 16 >= r11 * 256 * 15) waves = 11;
+    }
     if (ns != 2 && Aeff >= 32 && !narrow)
         while (waves < 16 && (long long)units * L.nXB * ceil_div(H, 2 * waves * ppt) >= 200 && waves * ppt < H) waves *= 2;
     while (waves > 1 && (waves / 2) * ppt >= H) waves /= 2;   // tiny slices: no more rows per tile than the slice has
@@ -1484,13 +1516,19 @@ static int launch_bwd_planned(const float *gsino_dev, int S, int H, int W, int P
     const unsigned inv_tiles = is_short ? div_magic_floor((unsigned)(L.nXB * tiles_y)) : (small ? div_magic((unsigned)(L.nXB * tiles_y)) : 0u);
     const unsigned inv_nxb = is_short ? div_magic_floor((unsigned)L.nXB) : div_magic((unsigned)L.nXB);
     const unsigned stage_magic = is_short && PW % 4 == 0 && (reinterpret_cast<uintptr_t>(gsino_dev) & 15) == 0 ? contig_rows_magic(PW) : 0u;
+    // SHORT launches read the dwords of their last index vector from the plan's compact tail section where it has one (A mod 16 = 1 ..
+    // 12: 1 .. 3 dwords per owned row where the uint4 is 4; at the headline shape 20 index bytes per pixel and row where the parent
+    // loaded 32).  Knob BWD_TAIL = 0: the uint4, as before the section existed.  Same taps, same order: same bits.
+    CTPVAE_REQUIRE(!is_short || H <= 65535, "rotate_bwd_planned: at most 65535 rows (as rotate_plan_build)");   // (32-bit byte offsets into the plan)
+    const int tail_t = is_short && knob(kKnobBwdTail) != 0 ? bwd_tail_dwords(A, dup) : 0;
+    const unsigned idx_req = !is_short ? 0u : (tail_t ? kIdxReqTail1 << (tail_t - 1) : kIdxReqTailWhole) | (tail_t == 0 || A > 16 ? kIdxReqFirst : 0u);
     auto launch = [&](auto kernel) -> int {
         static std::atomic<unsigned long long> attr_set{0}, abs_ok{0};   // per kernel instantiation: devices done
         CTPVAE_REQUIRE_NO_STATIC_LDS(kernel, "rotate_bwd_planned_kernel", abs_ok);
         CTPVAE_SET_MAX_LDS_ONCE(kernel, attr_set);
         hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(64 * waves), shmem, (hipStream_t)stream, gsino_dev, g, L,
                            (const uint4 *)bwd_plan_dev, tiles_y, S, SliceScale{scale_dev, scale_stride}, gimg_dev,
-                           inv_tiles, inv_nxb, stage_magic);
+                           inv_tiles, inv_nxb, stage_magic, idx_req);
         return CTPVAE_OK;
     };
     // The gradient image's stores.  A launch ends by writing its dirty L2 lines back (3.28 MB of them at the headline batch) before a

@@ -230,7 +230,11 @@ int ctpvae_rotate_bwd_scaled_f32(const float *gsino_dev, int S, int A, int PH, i
  * ctpvae_rotate_fwd_f32 / ctpvae_rotate_bwd_f32(mode TF_COMPAT) with interp NEAREST.
  * which: 0 = forward plan, 1 = backward (TF_COMPAT) plan.  _supported returns 1 if the geometry fits the planned
  * kernels (slice / cotangent block must fit LDS), else 0 -- use the direct entry points then.
- * Plan buffers are caller-owned device memory of ctpvae_rotate_plan_bytes() bytes, 256-byte aligned. */
+ * Plan buffers are caller-owned device memory of ctpvae_rotate_plan_bytes() bytes, 256-byte aligned.
+ * The backward plan is one 16-byte vector per (group of sixteen angles, row, padded column) -- a byte per angle, 255 = no
+ * tap -- and, when A mod 16 is 1 .. 12, behind that array (256-byte aligned) a compact tail section: the last group's
+ * live dwords once more, ceil((A mod 16) / 4) = 1 .. 3 per (row, padded column), the column running fastest.  Launches of
+ * at most 32 angles read their last group from the section; the array stays complete, every other launch reads it alone. */
 int ctpvae_rotate_plan_supported(int H, int W, int PH, int PW, int A, int interp, int which);
 long long ctpvae_rotate_plan_bytes(int H, int W, int PH, int PW, int A, int which);
 /* T8_dev: forward rows (needed for the forward plan); Tinv8_dev: inverted rows (needed for the backward plan);
