@@ -1,5 +1,15 @@
 """noise="poisson" without a GPU: the evaluation form's error against float64 (and the textbook form's, which it replaces), the
-edge cases of the definition, the ABI, argument checks, and the register / trap gates over the new kernels."""
+edge cases of the definition, the ABI, argument checks, and the register / trap gates over the new kernels.
+
+The per-sample rule of tests/np_twin_poisson.py (|got - ref| <= MARGIN * R * bar, the rule the GPU tests hold the kernels to) is
+checked here from the other side: the float32 twin stays within R_MAX bars of the float64 reference on every operand kind, the
+operand kinds sit on the seams they are named after, reference_dlogp is float64 autograd of reference_logp's formula, and four
+wrong twins -- a lost series term, a lost logf(lam / k) branch, a lost mask factor, a lost k == 0 case -- are refused.
+
+Seen here (seven kinds x pnm in {1, 1e2, 1e4, 1e6} at (5, 12, 184), and (3, 20, 9001) with one kind per pnm): the twin's worst
+excess is 0.41 .. 0.92 for lp and 0.18 .. 0.81 for dlp, so R = 1 everywhere.  The series without 1 / (360 k^3) reaches 12.3 bars on
+seam_k (allowed: 4) while the older bar_from_twin rule passes it at 0.2 of its bar; log1pf taken everywhere reaches 1.06e3 bars on
+small_k."""
 import os
 import re
 import shutil
@@ -178,3 +188,139 @@ def test_no_device_trap_in_the_poisson_kernels():
                 seen += 1
                 assert "s_trap" not in m.group(2), m.group(1)
     assert seen == 2 + 12 + 3
+
+
+# ---- the per-sample rule (tests/np_twin_poisson.py bar_logp / bar_dlogp) ------------------------------------------------------------
+RULE_PNMS = (1.0, 1e2, 1e4, 1e6)
+RULE_SHAPE = (5, 12, 184)
+RULE_BIG = (3, 20, 9001)                    # the GPU test's launch past one grid
+RULE_BIG_CASES = ((1.0, "near"), (1e2, "seam_k"), (1e4, "seam_u"), (1e6, "small_k"))      # one kind per pnm
+RULE_SEED = 11
+WHAT = ("logp", "dlogp")
+
+
+def rule_excess(what, fn, a):
+    want, bar = getattr(tw, "reference_" + what)(*a), getattr(tw, "bar_" + what)(*a)
+    return tw.worst_excess_bar(fn(*a), want, bar)
+
+
+def twin_within_the_bars(kind, shape, pnm):
+    a = tw.operands(kind, shape, pnm, RULE_SEED) + (pnm,)
+    r = {}
+    for what in WHAT:
+        r[what], same = rule_excess(what, getattr(tw, "twin_" + what), a)
+        assert same, f"{kind} {what}: the twin's non-finite samples differ in kind from the reference's"
+    print(f"[poisson] twin vs float64, {kind} pnm {pnm:g} {shape}: R lp {max(1.0, r['logp']):.2f} dlp {max(1.0, r['dlogp']):.2f} "
+          f"(worst excess lp {r['logp']:.2f} dlp {r['dlogp']:.2f})")
+    for what in WHAT:
+        assert max(1.0, r[what]) <= tw.R_MAX, f"{kind} {what}: the twin misses its own bar by {r[what]:.2f} > R_MAX"
+    # the exact zeros of the rule: a masked-out sample without counts
+    m = np.broadcast_to(a[1][..., None], a[0].shape)
+    zero = (m == 0) & (a[2] == 0)
+    assert (tw.bar_logp(*a)[zero] == 0).all() and (tw.bar_dlogp(*a)[zero] == 0).all()
+    assert (tw.twin_logp(*a)[zero] == 0).all() and (tw.twin_dlogp(*a)[zero] == 0).all()
+
+
+@pytest.mark.parametrize("pnm", RULE_PNMS)
+@pytest.mark.parametrize("kind", tw.KINDS)
+def test_twin_within_the_bars_of_the_reference(kind, pnm):
+    twin_within_the_bars(kind, RULE_SHAPE, pnm)
+
+
+@pytest.mark.parametrize("pnm,kind", RULE_BIG_CASES)
+def test_twin_within_the_bars_past_one_grid(pnm, kind):
+    twin_within_the_bars(kind, RULE_BIG, pnm)
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 65), RULE_SHAPE, RULE_BIG], ids=lambda s: "x".join(map(str, s)))
+def test_operands_are_what_they_say(shape):
+    """Conditions, not measurements: each kind puts the stated share of its samples where its name says, in float32 as the twin (and
+    the kernel) evaluates k, lam and u."""
+    F = np.float32
+    assert tw.KINDS == ("near", "far", "zero", "tiny", "seam_k", "seam_u", "small_k")
+    for pnm in RULE_PNMS:
+        def klu(kind):
+            proj, mask, x = tw.operands(kind, shape, pnm, RULE_SEED)
+            assert proj.dtype == mask.dtype == x.dtype == F and proj.shape == x.shape == shape and mask.shape == shape[:2]
+            if kind in tw.SEAM_KINDS:
+                assert set(np.unique(mask)) <= set(F(tw.MASKS[1:])) and (mask > 0).all()
+            k, lam = x * F(pnm), (proj * mask[..., None]) * F(pnm)
+            with np.errstate(all="ignore"):
+                return k, lam, (lam - k) / k
+        k, lam, u = klu("seam_k")
+        assert (k < 8).mean() >= 0.4 and (k >= 8).mean() >= 0.4
+        assert (np.abs(k.astype(np.float64) - 8.0) <= 1e-5 * 8.0).mean() >= 0.3
+        assert k.reshape(-1)[0] == 8 and (k < 8).any() and (lam > 0).all()
+        k, lam, u = klu("seam_u")
+        assert (u < F(-0.5)).mean() >= 0.4 and (u >= F(-0.5)).mean() >= 0.4
+        assert (np.abs(u.astype(np.float64) + 0.5) < 1e-5).mean() >= 0.3
+        k, lam, u = klu("small_k")
+        assert (k < 8).all() and (k > 0).all() and (k != np.round(k)).all()
+        assert (u < F(-0.5)).mean() >= 0.25
+    proj, mask, x = tw.operands("near", shape, 1.0, RULE_SEED)      # pnm 1: all three regimes of k in one launch
+    k = x * F(1.0)
+    assert (k == 0).mean() > 0.2 and ((k > 0) & (k < 8)).mean() > 0.2 and (k >= 8).mean() > 0.2
+    for kind in tw.KINDS[:4]:               # delegated: the Gaussian file's operands, bit for bit
+        for got, want in zip(tw.operands(kind, shape, 1e4, 3), tw.tg.operands(kind, shape, 1e4, 3)):
+            np.testing.assert_array_equal(got, want)
+    with pytest.raises(ValueError):
+        tw.operands("other", (1, 1, 1), 1e4, 0)
+
+
+@pytest.mark.parametrize("pnm", RULE_PNMS)
+def test_reference_dlogp_is_float64_autograd_of_reference_logp(pnm):
+    """d / d proj of xlogy(k, lam) - lgamma(k + 1) - lam (reference_logp's formula; k == 0: -lam) by float64 torch autograd, on the
+    samples with lam > 0.
+
+    Autograd returns m pnm k / lam - m pnm, the reference m pnm (k - lam) / lam: two float64 evaluations of the same number whose
+    operations each round a value no larger than m pnm (k / lam + 1) -- three on either side, so they differ by at most
+    8 * 2^-53 * m pnm (k / lam + 1) per sample."""
+    worst = 0.0
+    for kind in tw.KINDS:
+        proj, mask, x = tw.operands(kind, (4, 5, 8), pnm, seed=2)
+        p = torch.from_numpy(proj.astype(np.float64)).requires_grad_(True)
+        m = torch.from_numpy(mask.astype(np.float64))[..., None]
+        k = torch.from_numpy(x.astype(np.float64)) * float(np.float32(pnm))
+        lam = p * m * float(np.float32(pnm))
+        lp = torch.where(k == 0, -lam, torch.xlogy(k, torch.where(k == 0, torch.ones_like(lam), lam)) - torch.lgamma(k + 1) - lam)
+        on = (lam > 0).numpy()
+        assert on.any()
+        # the same formula (a check of the expression, not of float64: torch's and scipy's lgamma and log differ by a few ulp of
+        # the three terms, 1e-16 relative -- any other formula differs by 1e-2 and more)
+        kn, ln = k.numpy()[on], lam.detach().numpy()[on]
+        terms = np.abs(kn * np.log(ln)) + np.abs(torch.lgamma(k + 1).numpy()[on]) + ln + 1.0
+        assert (np.abs(lp.detach().numpy()[on] - tw.reference_logp(proj, mask, x, pnm)[on]) <= 1e-12 * terms).all()
+        lp.sum().backward()
+        got, want = tw.reference_dlogp(proj, mask, x, pnm)[on], p.grad.numpy()[on]
+        assert np.isfinite(want).all()
+        allowed = 8.0 * 2.0 ** -53 * np.broadcast_to(m.numpy() * float(np.float32(pnm)), on.shape)[on] * (kn / ln + 1.0)
+        ratio = float((np.abs(got - want) / allowed).max())
+        worst = max(worst, ratio)
+        assert ratio <= 1.0, f"{kind}: {ratio:.3f}"
+    print(f"[poisson] reference_dlogp vs float64 autograd, pnm {pnm:g}: worst |difference| / allowed {worst:.3f}")
+
+
+WRONG_TWINS = (("logp", "without_c2", tw.twin_logp_without_c2, "seam_k"), ("logp", "always_log1p", tw.twin_logp_always_log1p, "small_k"),
+               ("dlogp", "without_mask", tw.twin_dlogp_without_mask, "near"), ("dlogp", "general_at_zero", tw.twin_dlogp_general_at_zero, "zero"))
+
+
+@pytest.mark.parametrize("pnm", RULE_PNMS)
+@pytest.mark.parametrize("what,name,fn,kind", WRONG_TWINS, ids=[w[1] for w in WRONG_TWINS])
+def test_the_rule_refuses_wrong_twins(what, name, fn, kind, pnm):
+    """Negative controls: each wrong twin exceeds MARGIN * R * bar on at least one sample of the kind named for it, or differs in
+    kind there, while the correct twin passes on the same operands.  The series without its second term passes the older
+    bar_from_twin rule on those operands -- which is why that rule is not enough."""
+    a = tw.operands(kind, RULE_SHAPE, pnm, RULE_SEED) + (pnm,)
+    want, bar = getattr(tw, "reference_" + what)(*a), getattr(tw, "bar_" + what)(*a)
+    R = tw.twin_ratio(getattr(tw, "twin_" + what)(*a), want, bar)
+    right, right_same = tw.worst_excess_bar(getattr(tw, "twin_" + what)(*a), want, bar)
+    worst, same = tw.worst_excess_bar(fn(*a), want, bar)
+    print(f"[poisson] negative control '{name}', {kind} pnm {pnm:g}: worst excess {worst:.3g}, same kinds {same}, against MARGIN R = "
+          f"{tw.MARGIN * R:.1f}; the correct twin {right:.2f}")
+    assert R <= tw.R_MAX and right_same and right <= tw.MARGIN * R
+    assert worst > tw.MARGIN * R or not same, f"the rule accepts '{name}' on {kind}"
+    if name == "without_c2":
+        _, atol, rtol, _, _ = tw.bar_from_twin(*a)
+        old, _, old_same = tw.worst_excess(fn(*a), want, atol, rtol)
+        print(f"[poisson] negative control '{name}', {kind} pnm {pnm:g}: worst |err| / (atol + rtol |want|) under bar_from_twin {old:.2f}")
+        assert old_same and old <= 1.0, "bar_from_twin was expected to pass the series without its second term"
