@@ -160,6 +160,11 @@ SIGNATURES = {
     "ctpvae_tn_head_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
     "ctpvae_tn_head_uniforms_host_f32": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp]),
+    "ctpvae_beta_head_fwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _c_float, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    "ctpvae_beta_head_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _c_float, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    "ctpvae_beta_head_words_host_u32": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _c_int, _c_int, _vp]),
     "ctpvae_tn_marginals_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, ctypes.c_uint]),
     "ctpvae_tn_marginals_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                          _c_float, _c_float, _c_int, _vp, _vp, _vp, _vp, _vp]),

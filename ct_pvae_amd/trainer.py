@@ -40,6 +40,7 @@ from .forward_functions import num_proj_pix
 from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
 from .latents import normal_latents
 from .marginals import PixelMarginals
+from .beta_head import beta_head
 from .output_head import truncated_normal_head
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -281,16 +282,24 @@ def kl_normal_std(loc, scale):
 # ---------------------------------------------------------------------------------------------------------
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
-                        use_normal=True, model="rotate", noise="gaussian", fused_head=None, fused_latents=None):
+                        use_normal=True, model="rotate", noise="gaussian", fused_head=None, fused_latents=None,
+                        fused_beta_head=None):
     """fused_head: None -- the output distribution is the chain of torch operations below, its uniforms from torch's global
     generator -- or (seed, draw, first_object): sample, log-density and its per-object sum come from ONE launch
     (output_head.truncated_normal_head, csrc/head.hip), the uniforms from Philox keyed by those three; --normal only.
     fused_latents: None -- the Normal latents and their KL term are the chain of torch operations below, the draws from torch's
     global generator -- or (seed, draw, first_object): per skip level ONE launch gives the ns samples and the per-object KL
     (latents.normal_latents, csrc/latent.hip), the draws from Philox keyed by those three, the level and the sample; first_object is
-    the offset of this call's objects in the GLOBAL batch; --normal only, not with deterministic."""
+    the offset of this call's objects in the GLOBAL batch; --normal only, not with deterministic.
+    fused_beta_head: None, or (seed, draw, first_object): the DEFAULT Beta output head (use_normal=False) -- sample, clamp, log-density
+    and its per-object sum -- comes from ONE launch (beta_head.beta_head, csrc/beta_head.hip), the draws from Philox keyed by those
+    three, the gradient TensorFlow's implicit one.  Allowed with deterministic=True: the reference samples the output distribution
+    there too."""
     if fused_head is not None and not use_normal:
-        raise ValueError("fused_head is the TruncatedNormal output head: it needs use_normal=True (the Beta head is not fused)")
+        raise ValueError("fused_head is the TruncatedNormal output head: it needs use_normal=True (the Beta head is fused_beta_head)")
+    if fused_beta_head is not None and use_normal:
+        raise ValueError("fused_beta_head is the Beta output head: it needs use_normal=False (with use_normal=True the output is "
+                         "TruncatedNormal: fused_head)")
     if fused_latents is not None and (not use_normal or deterministic):
         raise ValueError("fused_latents is the Normal latent block: it needs use_normal=True and deterministic=False (the Beta latents "
                          "are not fused)")
@@ -335,6 +344,10 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
         dist = TruncatedNormal(positive_range(alpha), positive_range(beta), low=0.0, high=1e10)
         output_sample = dist.rsample()                                   # [ns * B][1][X][Y]
         log_prob_R_given_z = dist.log_prob(output_sample)
+    elif fused_beta_head is not None:                               # :278-285 in one launch
+        seed, draw, first_object = fused_beta_head
+        x, head_lp = beta_head(alpha.contiguous(), beta.contiguous(), seed=seed, draw=draw, first_object=first_object, sqrt_reg=sqrt_reg)
+        output_sample = x.permute(0, 3, 1, 2)
     else:                                                           # :278-285
         dist = torch.distributions.Beta(positive_range(alpha), positive_range(beta))
         output_sample = dist.rsample()
@@ -346,7 +359,7 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     # :305-306 reduce_sum(..., axis=[0, 1, 2]) of the squeezed [B][A][P] and [B][X][Y] tensors: the log-likelihood of a
     # sample is ONE number for the whole batch (the batch axis is summed too), the KL below is per object; :329-330 then
     # broadcast-subtract, and train_step takes the mean over the batch -- i.e. mean_b(KL_b) - sum_b(loglik_b).
-    if fused_head is None:
+    if fused_head is None and fused_beta_head is None:
         head_lp = log_prob_R_given_z.sum(dim=(1, 2, 3))
     log_prob_M = (lp + head_lp).view(ns, B).sum(dim=1)                                    # [ns]
     recon = output_sample[(ns - 1) * B:]
@@ -381,7 +394,10 @@ class AngleStream:
 
 
 _PIXEL_DIST_NEEDS = ("--pixel_dist samples the TruncatedNormal output head of sampled Normal latents: it needs --normal and cannot be "
-                     "combined with --det (the Beta head is not sampled by any kernel)")
+                     "combined with --det (there are no marginals of the Beta head)")
+
+
+_FUSED_BETA_HEAD_NEEDS = "--fused_beta_head is the default Beta output head: it cannot be combined with --normal (there: --fused_head)"
 
 
 class PVAETrainer:
@@ -389,6 +405,8 @@ class PVAETrainer:
         self.args, self.dev = args, device
         if getattr(args, "fused_head", False) and not args.use_normal:
             raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
+        if getattr(args, "fused_beta_head", False) and args.use_normal:
+            raise ValueError(_FUSED_BETA_HEAD_NEEDS)
         if getattr(args, "fused_latents", False) and (not args.use_normal or args.deterministic):
             raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
         if getattr(args, "pixel_dist", False) and (not args.use_normal or args.deterministic):
@@ -521,6 +539,9 @@ class PVAETrainer:
         fused = None
         if getattr(a, "fused_head", False):
             fused = (a.head_seed, self.iter, self.rank * (1 if a.deterministic else a.ns) * input_encode.shape[0])
+        fused_beta = None                  # --fused_beta_head: keyed exactly as --fused_head
+        if getattr(a, "fused_beta_head", False):
+            fused_beta = (a.head_seed, self.iter, self.rank * (1 if a.deterministic else a.ns) * input_encode.shape[0])
         # --fused_latents: the same seed and draw; the latents' objects are counted in the GLOBAL batch (the sample index is a counter
         # word of its own), so their draws are the same at every world size
         fused_lat = None
@@ -539,7 +560,7 @@ class PVAETrainer:
                                                           theta=self.theta_host, angles_i=angles_i, pad=self.pad,
                                                           deterministic=a.deterministic, use_normal=a.use_normal,
                                                           model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
-                                                          fused_head=fused, fused_latents=fused_lat)
+                                                          fused_head=fused, fused_latents=fused_lat, fused_beta_head=fused_beta)
         finally:
             if self.enc_drop is not None:
                 self.enc_drop.clear(), self.dec_drop.clear()
@@ -778,6 +799,10 @@ def get_args(argv=None):
     p.add_argument("--fused_head", action="store_true",
                    help="sample the TruncatedNormal output and sum its log-density in one launch (csrc/head.hip), with Philox uniforms "
                         "keyed by (--head_seed, step index, object) instead of torch's global generator; needs --normal")
+    p.add_argument("--fused_beta_head", action="store_true",
+                   help="sample the default Beta output and sum its clamped log-density in one launch (csrc/beta_head.hip), with "
+                        "Philox draws keyed by (--head_seed, step index, object) instead of torch's global generator and TensorFlow's "
+                        "implicit reparameterisation gradient instead of torch's direct Beta derivative; not with --normal")
     p.add_argument("--fused_latents", action="store_true",
                    help="sample the Normal latents and sum their KL term in one launch per skip level (csrc/latent.hip), with Philox "
                         "draws keyed by (--head_seed, step index, level, sample, global object) instead of torch's global generator; "
@@ -798,7 +823,7 @@ def get_args(argv=None):
     p.add_argument("--reproducible", action="store_true",
                    help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
                         "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")
-    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's uniforms and of --fused_latents' draws")
+    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's and --fused_beta_head's uniforms and of --fused_latents' draws")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")
@@ -840,6 +865,8 @@ def get_args(argv=None):
     args = p.parse_args(argv)
     if args.fused_head and not args.use_normal:
         raise ValueError("--fused_head is the TruncatedNormal output head: it needs --normal")
+    if args.fused_beta_head and args.use_normal:
+        raise ValueError(_FUSED_BETA_HEAD_NEEDS)
     if args.fused_latents and (not args.use_normal or args.deterministic):
         raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
     if args.pixel_dist and (not args.use_normal or args.deterministic):

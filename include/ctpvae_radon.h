@@ -719,6 +719,28 @@ int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n,
                            float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream);
 int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host);
 
+/* ---- the Beta output head (added at ABI 3400): the P-VAE decoder's default output distribution, Beta(pr(alpha), pr(beta)), as one
+ * forward and one backward launch (csrc/beta_head.hip states the function, the stream, the order of the per-object sum and the
+ * backward's arithmetic).  alpha_dev, beta_dev [n][pix] fp32, the decoder's raw outputs; 0 < sqrt_reg < 0.5 is the clamp of the sample
+ * inside the log-density.  The draws of pixel `pixel` of object o are words 0 .. 2 of the blocks
+ *   Philox4x32-10((lo32(e), hi32(e), draw, 0x42000000 | gamma << 8 | attempt), key = seed),  e = (first_object + o) * pix + pixel,
+ * one block per (pixel, gamma, attempt), attempt < 16.
+ *   _fwd_f32: x_out_dev [n][pix] the sample (not clamped), lp_sum_out_dev [n] the per-object sum of the log-densities (fixed order),
+ *     lp_elem_out_dev [n][pix] or NULL, aux_out_dev [n][pix][2][4] or NULL: (zn, ub, attempt, lg) of the accepted attempt of each gamma
+ *     (tests only).
+ *   _bwd_f32: g_alpha_out_dev, g_beta_out_dev [n][pix] for the cotangents g_x_dev [n][pix] and g_lp_dev [n] (either may be NULL: zero):
+ *     the implicit reparameterisation gradient of each gamma.  Nothing is saved by the forward: the backward redraws.
+ *   _words_host_u32: the Philox words of one (gamma, attempt) into HOST memory out_host [n][pix][4]; needs no GPU.
+ * n * pix <= 2^31 - 1; first_object >= 0. */
+int ctpvae_beta_head_fwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                             unsigned long long seed, unsigned draw, float sqrt_reg, float *x_out_dev, float *lp_sum_out_dev,
+                             float *lp_elem_out_dev, float *aux_out_dev, ctpvae_stream_t stream);
+int ctpvae_beta_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                             unsigned long long seed, unsigned draw, float sqrt_reg, const float *g_x_dev, const float *g_lp_dev,
+                             float *g_alpha_out_dev, float *g_beta_out_dev, ctpvae_stream_t stream);
+int ctpvae_beta_head_words_host_u32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, int gamma,
+                                    int attempt, unsigned *out_host);
+
 /* ---- per-pixel marginals of the TruncatedNormal output head (the reference's CT_VAE.pixel_dist, ctvae/main_ct_vae.py:648-731): the
  * histogram, the sum and the sum of squares of the samples of every pixel, with no sample written to memory (csrc/marginals.hip
  * states the layout and the fixed order of the float64 sums).  alpha_dev, beta_dev [n][pix] as for ctpvae_tn_head_fwd_f32.  The launch
