@@ -4,6 +4,9 @@
     words(n, pix, seed, draw, fo)        uint32 [n][pix][2][16][4]: the Philox block of every (pixel, gamma, attempt), numpy
     search(alpha, beta, words, dtype)    the Marsaglia-Tsang attempt loop restated: the accepted attempt k, its (zn, ub), the float
                                          acceptance margin of every attempt and a float32 bar of that margin
+    search_lazy(alpha, beta, seed, draw, dtype)
+                                         the same k, zn, ub from the Philox blocks of the attempts a gamma reaches alone (2^20 pixels:
+                                         the law tests, tests/test_beta_head_law_cpu.py), with the law tests' wrong samplers
     compose(alpha, beta, draws, dtype)   the composition of beta_head.hip's header at GIVEN accepted draws (zn, ub) [n][pix][2];
                                          float64: the definition, on the float32 operands and constants promoted; float32: the twin
                                          in the kernel's form (fp32 forward; the backward in float64 on the fp32 intermediates, as the
@@ -94,10 +97,10 @@ def _pr(t, dt):
     return np.where(t >= 1, t, e + dt(EPS32)), np.where(t >= 1, dt(1), e)
 
 
-def _consts(c, dt):
+def _consts(c, dt, defect=None):
     cb = np.where(c < 1, c + dt(1), c)
     third = dt(F(1) / F(3)) if dt is F else dt(1) / dt(3)
-    d = cb - third
+    d = cb if defect == "d_is_cb" else cb - third
     return d, dt(1) / np.sqrt(dt(9) * d)
 
 
@@ -124,6 +127,50 @@ def search(alpha, beta, w, dtype):
     k = np.where(ok.any(axis=-1), ok.argmax(axis=-1), ATTEMPTS - 1)
     take = lambda a: np.take_along_axis(a, k[..., None], axis=-1)[..., 0]                 # noqa: E731
     return dict(k=k, zn=take(zn32), ub=take(np_twin_hmc.u24(w[..., 2])), margin=margin, bar=np.where(np.isfinite(bar), bar, np.inf).astype(D))
+
+
+SEARCH_DEFECTS = (None, "no_squeeze", "no_half_zn2", "d_is_cb")
+
+
+def search_lazy(alpha, beta, seed, draw, dtype, first_object=0, defect=None, cache=None):
+    """search() without the words of attempts nobody reaches: attempt 0 of every gamma, then attempt k of those still refused only
+    (their Philox blocks alone).  dict k, zn, ub [n][pix][2] -- equal to search's on the words of (seed, draw, first_object).
+    defect (negative controls of the law tests; compose takes the matching one where lg changes too): "no_squeeze" accepts the first
+    attempt with w > 0, "no_half_zn2" drops 0.5 zn^2 from the squeeze, "d_is_cb" takes d = cb.  cache: a dict that keeps attempt 0's
+    words between calls on ONE (shape, seed, draw, first_object) -- the two dtypes and the defects draw the same."""
+    assert defect in SEARCH_DEFECTS
+    dt = dtype
+    n, pix = np.shape(alpha)
+    c = np.stack([_pr(alpha, dt)[0], _pr(beta, dt)[0]], axis=-1)                           # [n][pix][2]
+    d, s = (np.broadcast_to(v, c.shape).ravel() for v in _consts(c, dt, defect))
+    e = ((np.uint64(first_object) + np.arange(n, dtype=np.uint64))[:, None] * np.uint64(pix) + np.arange(pix, dtype=np.uint64)[None, :])
+    e, j = np.broadcast_to(e[..., None], c.shape).ravel(), np.broadcast_to(np.arange(2, dtype=np.uint64), c.shape).ravel()
+    k = np.full(e.size, ATTEMPTS - 1, np.int64)
+    zn_out, ub_out = np.zeros(e.size, F), np.zeros(e.size, F)
+    live = np.arange(e.size)
+    for att in range(ATTEMPTS):
+        el, tag = e[live], np.uint64(TAG) | (j[live] << np.uint64(8)) | np.uint64(att)
+        if att == 0 and cache is not None and "w0" in cache:
+            w = cache["w0"]
+        else:
+            w = np_twin_hmc.philox(el & np.uint64(0xFFFFFFFF), el >> np.uint64(32), np.uint64(draw), tag, int(seed))
+        if att == 0 and cache is not None:
+            cache["w0"] = w
+        zn32 =special.ndtri(np_twin_hmc.u24(w[..., 0]).astype(F)).astype(F)
+        zn, ua, dl, sl = zn32.astype(dt), np_twin_hmc.u24(w[..., 1]).astype(dt), d[live], s[live]
+        with np.errstate(all="ignore"):
+            wv = dt(1) + sl * zn
+            v = (wv * wv) * wv
+            half = dt(0) if defect == "no_half_zn2" else dt(0.5) * (zn * zn)
+            rhs = ((half + dl) - dl * v) + dl * np.log(v)
+            ok = (wv > 0) & ((np.log(ua) < rhs) | (defect == "no_squeeze"))
+        zn_out[live], ub_out[live] = zn32, np_twin_hmc.u24(w[..., 2])                       # (the last attempt's where all refuse)
+        k[live[ok]] = att
+        live = live[~ok]
+        if live.size == 0:
+            break
+    shape = c.shape
+    return dict(k=k.reshape(shape), zn=zn_out.reshape(shape), ub=ub_out.reshape(shape))
 
 
 # ---- float64 special functions ----------------------------------------------------------------------------------------------------
@@ -208,23 +255,26 @@ _dlg_like = dlg
 def compose(alpha, beta, draws, dtype, sr=EPS32, lg=None, defect=None):
     """The composition at accepted draws (zn, ub), each float32 [n][pix][2], in `dtype`: a dict of numpy arrays of that dtype
     (gamma-wise quantities [n][pix][2]: index 0 is a's gamma, 1 is b's).  lg [n][pix][2] (tests): the gammas' logarithms given
-    instead of computed from the draws.  defect (negative control): "one_minus_x" takes y as 1 - x."""
-    assert defect in (None, "one_minus_x")
+    instead of computed from the draws.  defect (negative controls): "one_minus_x" takes y as 1 - x; the law tests' "d_is_cb" takes
+    d = cb, "no_boost" leaves the boost out, "boost_cb" divides it by cb = c + 1."""
+    assert defect in (None, "one_minus_x", "d_is_cb", "no_boost", "boost_cb")
     lg_given = lg
     dt = dtype
     zn, ub = (np.asarray(v, F).astype(dt) for v in draws)
     t = np.stack([np.asarray(alpha, F), np.asarray(beta, F)], axis=-1)
     c, dc = _pr(t, dt)
-    d, s = _consts(c, dt)
+    d, s = _consts(c, dt, defect)
     sr, hi = dt(F(sr)), dt(F(1) - F(sr))
     with np.errstate(all="ignore"):
         w = dt(1) + s * zn
         v = np.where(w <= 0, dt(1), (w * w) * w)
         logd, logv = np.log(d), np.log(v)
-        boost = np.where(c < 1, np.log(ub) / c, dt(0))
+        boost = np.where(c < 1, np.log(ub) / (c + dt(1) if defect == "boost_cb" else c), dt(0))
+        if defect == "no_boost":
+            boost = np.zeros_like(boost)
         lg = (logd + logv) + boost if lg_given is None else np.asarray(lg_given).astype(dt)
         x = dt(1) / (dt(1) + np.exp(lg[..., 1] - lg[..., 0]))
-        y = dt(1) / (dt(1) + np.exp(lg[..., 0] - lg[..., 1])) if defect is None else dt(1) - x
+        y = dt(1) / (dt(1) + np.exp(lg[..., 0] - lg[..., 1])) if defect != "one_minus_x" else dt(1) - x
         lo_y = dt(1) - hi                                            # x > hi is tested as y < 1 - hi, the kernel's form
         passes = (x >= sr) & (y >= lo_y)
         xc = np.where(x < sr, sr, np.where(y < lo_y, hi, x))
@@ -240,10 +290,11 @@ def compose(alpha, beta, draws, dtype, sr=EPS32, lg=None, defect=None):
     return out
 
 
-def gradients(c, g_x, g_LP, defect=None):
+def gradients(c, g_x, g_LP, defect=None, dlg_=None, defect_scale=1.0):
     """(g_alpha, g_beta) of the composition's dtype: float64 arithmetic on the composition's intermediates (promoted), the closed form
     of beta_head.hip's header; rounded to float32 once when the composition is the float32 twin.  defect (negative controls):
-    "dlg_1e-4" scales dlg by 1 + 1e-4, "no_gate" lets lp's path through x pass the clamp."""
+    "dlg_1e-4" scales dlg by 1 + 1e-4 * defect_scale, "no_gate" lets lp's path through x pass the clamp.  dlg_ = (d0, d1): the
+    float64 dlg of the two gammas computed before (several cotangents on one composition)."""
     assert defect in (None, "dlg_1e-4", "no_gate")
     dt = c["x"].dtype.type
     a, b, x, y, xc, yc = (c[k].astype(D) for k in ("a", "b", "x", "y", "xc", "yc"))
@@ -254,9 +305,9 @@ def gradients(c, g_x, g_LP, defect=None):
         gx0 = np.where(c["passes"] | (defect == "no_gate"), gx + G * ((a - 1.0) / xc - (b - 1.0) / yc), gx)
         xy = x * y
         dead = (gx0 == 0.0) | (xy == 0.0)
-        d0, d1 = _dlg_like(a, lg[..., 0]), _dlg_like(b, lg[..., 1])
+        d0, d1 = (_dlg_like(a, lg[..., 0]), _dlg_like(b, lg[..., 1])) if dlg_ is None else dlg_
         if defect == "dlg_1e-4":
-            d0, d1 = d0 * (1 + 1e-4), d1 * (1 + 1e-4)
+            d0, d1 = d0 * (1 + 1e-4 * defect_scale), d1 * (1 + 1e-4 * defect_scale)
         pa = np.where(dead, 0.0, gx0 * xy * d0)
         pb = np.where(dead, 0.0, -(gx0 * xy * d1))
         pab = digamma_kernel(a + b)

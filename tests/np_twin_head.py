@@ -82,8 +82,10 @@ def _positive_range(t, unit_slope):
 
 def compose(alpha, beta, u, dtype, defect=None):
     """The composition on float32 operands [n][pix] in `dtype`; returns a dict of torch tensors (alpha, beta are leaves that require
-    grad).  defect (negative controls): "no_log_z" drops log Z from lp, "unit_slope" makes pr' = 1."""
-    assert defect in (None, "no_log_z", "unit_slope")
+    grad).  defect (negative controls): "no_log_z" drops log Z from lp, "unit_slope" makes pr' = 1; the law tests' "z_is_1"
+    takes Z as 1 in p = Pa + u Z, "no_truncation" forgets the truncation in the draw altogether (p = u), "flip_lower" takes 1 - u for
+    u where p falls on the lower half."""
+    assert defect in (None, "no_log_z", "unit_slope", "z_is_1", "no_truncation", "flip_lower")
     al = torch.tensor(np.asarray(alpha, np.float32)).to(dtype).requires_grad_(True)
     be = torch.tensor(np.asarray(beta, np.float32)).to(dtype).requires_grad_(True)
     uu = torch.tensor(np.asarray(u, np.float32)).to(dtype)
@@ -92,7 +94,9 @@ def compose(alpha, beta, u, dtype, defect=None):
     Pa = 0.5 * (1 + torch.erf(a / math.sqrt(2.0)))
     cdf_b = 0.5 * (1 + torch.erf(((1e10 - loc) / scale) / math.sqrt(2.0)))
     Z = (cdf_b - Pa).clamp_min(1e-30)
-    p0 = Pa + uu * Z
+    p0 = uu if defect == "no_truncation" else Pa + uu * (1.0 if defect == "z_is_1" else Z)
+    if defect == "flip_lower":
+        p0 = torch.where(p0 < 0.5, Pa + (1 - uu) * Z, p0)
     p = p0.clamp(P_LO, P_HI)
     z = torch.special.ndtri(p)
     x0 = loc + scale * z
