@@ -12,6 +12,7 @@ from .fbp import iradon, iradon_all  # noqa: F401
 from .recon import crop, evaluate_sinogram, recon, siddon_backproject  # noqa: F401
 from .mcmc import hmc_sample  # noqa: F401
 from .beta_head import beta_head, beta_head_words  # noqa: F401
+from .beta_latents import beta_latent_words, beta_latents  # noqa: F401
 from .output_head import head_uniforms, truncated_normal_head  # noqa: F401
 from .latents import latent_draws, normal_latents  # noqa: F401
 from .marginals import PixelMarginals, bin_samples  # noqa: F401

@@ -175,6 +175,12 @@ SIGNATURES = {
                                        ctypes.c_uint, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_latent_draws_host_f32": (_c_int, [_c_int, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                               _vp]),
+    "ctpvae_beta_latent_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                            _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_beta_latent_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                            _vp, _vp, _vp, _vp]),
+    "ctpvae_beta_latent_words_host_u32": (_c_int, [_c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint, _c_int,
+                                                   _c_int, _c_int, _vp]),
     "ctpvae_periodic_pad_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ctpvae_periodic_pad_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ctpvae_maxout_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp]),

@@ -1,4 +1,5 @@
-// beta_head.h -- what beta_head.hip (the Beta output head) shares with the Beta kernels to come (latents, marginals): the layout of the
+// beta_head.h -- what beta_head.hip (the Beta output head) shares with beta_latent.hip (the Beta latents) and the Beta kernel to come
+// (marginals): the layout of the
 // random numbers, the log-space gamma sampler, the pixel's function and the implicit reparameterisation gradient of a gamma's
 // logarithm.  beta_head.hip's header states the function; every file evaluates it through this code alone, so one
 // (alpha, beta, e, draw, seed) gives one x wherever it is computed (-ffp-contract=off: the same operations, the same bits).
@@ -7,7 +8,8 @@
 
 namespace ctpvae {
 
-constexpr unsigned kBetaTag = 0x42000000u;   // "B": the fourth counter word is kBetaTag | gamma << 8 | attempt
+constexpr unsigned kBetaTag = 0x42000000u;   // "B": the head's fourth counter word is kBetaTag | gamma << 8 | attempt
+constexpr unsigned kBetaLatentTag = 0x51000000u;   // "Q": the latents' is kBetaLatentTag | level << 16 | s << 5 | gamma << 4 | attempt
 constexpr int kBetaAttempts = 16;            // Marsaglia-Tsang attempts per gamma: refusal <= 0.046 each, the cap binds with p < 1e-21
 constexpr int kDlgMaxTerms = 2048;           // hard bound on the iterations of beta_dlg's series / continued fraction
 constexpr float kBetaThird = 1.0f / 3.0f;
@@ -17,13 +19,20 @@ __host__ __device__ inline Philox4 beta_block(unsigned long long e, unsigned dra
     return philox4x32_10((unsigned)e, (unsigned)(e >> 32), draw, kBetaTag | (gamma << 8) | attempt, k0, k1);
 }
 
-// log of a Gamma(c, 1) sample: the accepted attempt's normal and boost uniform, its index, and lg = log(d) + log(v) + boost
+// the latents' fourth counter word without the attempt: level < 256, s < 2048, gamma 0 or 1 (the attempt takes bits 0 .. 3)
+__host__ __device__ inline unsigned beta_latent_word3(unsigned level, unsigned s, unsigned gamma)
+{
+    return kBetaLatentTag | (level << 16) | (s << 5) | (gamma << 4);
+}
+
+// log of a Gamma(c, 1) sample: the accepted attempt's normal and boost uniform, its index, and lg = log(d) + log(v) + boost.  word3 is
+// the fourth counter word WITHOUT the attempt (the head: kBetaTag | gamma << 8; the latents: beta_latent_word3); attempt k is ORed in here.
 struct BetaGamma {
     float zn, ub, lg;
     int k;
 };
 
-__device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long e, unsigned draw, unsigned j, unsigned k0, unsigned k1)
+__device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long e, unsigned draw, unsigned word3, unsigned k0, unsigned k1)
 {
     const float cb = c < 1.0f ? c + 1.0f : c;
     const float d = cb - kBetaThird;
@@ -32,7 +41,7 @@ __device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long 
     float v = 1.0f;
 #pragma unroll 1
     for (int k = 0; k < kBetaAttempts; ++k) {      // bounded by construction: a NaN operand refuses every attempt
-        const Philox4 blk = beta_block(e, draw, j, (unsigned)k, k0, k1);
+        const Philox4 blk = philox4x32_10((unsigned)e, (unsigned)(e >> 32), draw, word3 | (unsigned)k, k0, k1);
         const float zn = normcdfinvf(head_u24(blk.w[0])), ua = head_u24(blk.w[1]);
         const float w = 1.0f + s * zn;
         const float v3 = (w * w) * w;
@@ -62,8 +71,8 @@ __device__ __forceinline__ BetaPixel beta_pixel(float alpha, float beta, unsigne
     r.b = beta >= 1.0f ? beta : eb + kHeadEps;
     r.da = alpha >= 1.0f ? 1.0f : ea;
     r.db = beta >= 1.0f ? 1.0f : eb;
-    r.g0 = beta_log_gamma(r.a, e, draw, 0u, k0, k1);
-    r.g1 = beta_log_gamma(r.b, e, draw, 1u, k0, k1);
+    r.g0 = beta_log_gamma(r.a, e, draw, kBetaTag | (0u << 8), k0, k1);
+    r.g1 = beta_log_gamma(r.b, e, draw, kBetaTag | (1u << 8), k0, k1);
     r.x = 1.0f / (1.0f + expf(r.g1.lg - r.g0.lg));
     r.y = 1.0f / (1.0f + expf(r.g0.lg - r.g1.lg));
     // the upper bound is tested on y: x > hi <=> y < 1 - hi, and next to 1 y keeps the relative accuracy that x has lost
@@ -90,6 +99,45 @@ __device__ __forceinline__ double beta_digamma(double x)
     const double inv = 1.0 / x, i2 = inv * inv;
     const double series = i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132 - i2 * (691.0 / 32760 - i2 * (1.0 / 12)))))));
     return r + ((log(x) - 0.5 * inv) - series);
+}
+
+// lgamma(x) and digamma(x) together, x > 0, for the latents' KL term: ten straight-line steps of the recurrences lgamma(x) =
+// lgamma(x + 1) - log x and psi(x) = psi(x + 1) - 1 / x, each taken while x < 10 -- the factors multiplied into p and ONE logarithm
+// taken, the reciprocals kept as the fraction q / p (q <- q x + p: all terms positive, no cancellation) and ONE division made -- then,
+// with one logarithm and one reciprocal of the shifted x shared by both, Stirling's series (x - 1/2) log x - x + log(2 pi) / 2 + 1/12x
+// - 1/360x^3 + 1/1260x^5 - 1/1680x^7 + 1/1188x^9 - 691/360360x^11 + 1/156x^13 - 3617/122400x^15 (the next term is < 2e-17 at x = 10)
+// and beta_digamma's series.  No loop and no branch: the chains of several arguments overlap each other's latencies.  (The
+// library's float64 lgamma costs a kernel more than 128 registers.)
+__device__ __forceinline__ void beta_lgamma_digamma(double x, double &lg, double &psi)
+{
+    double p = 1.0, q = 0.0;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const bool low = x < 10.0;
+        q = low ? q * x + p : q;
+        p = low ? p * x : p;
+        x = low ? x + 1.0 : x;
+    }
+    const double inv = 1.0 / x, i2 = inv * inv, lx = log(x);
+    const double stirling = inv * (1.0 / 12 - i2 * (1.0 / 360 - i2 * (1.0 / 1260 - i2 * (1.0 / 1680 - i2 * (1.0 / 1188 - i2 * (691.0 / 360360 - i2 * (1.0 / 156 - i2 * (3617.0 / 122400))))))));
+    const double series = i2 * (1.0 / 12 - i2 * (1.0 / 120 - i2 * (1.0 / 252 - i2 * (1.0 / 240 - i2 * (1.0 / 132 - i2 * (691.0 / 32760 - i2 * (1.0 / 12)))))));
+    lg = ((((x - 0.5) * lx - x) + 0.91893853320467274178) + stirling) - log(p);
+    psi = ((lx - 0.5 * inv) - series) - q / p;
+}
+
+// trigamma(x), x > 0: the recurrence psi'(x) = psi'(x + 1) + 1 / x^2 up to x >= 10 (at most 10 steps), then the asymptotic series
+// 1/x + 1/2x^2 + 1/6x^3 - 1/30x^5 + 1/42x^7 - 1/30x^9 + 5/66x^11 - 691/2730x^13 + 7/6x^15 (the next term is < 4e-16 at x = 10).
+__device__ __forceinline__ double beta_trigamma(double x)
+{
+    double r = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < 10 && x < 10.0; ++i) {
+        r += 1.0 / (x * x);
+        x += 1.0;
+    }
+    const double inv = 1.0 / x, i2 = inv * inv;
+    const double series = i2 * (1.0 / 6 - i2 * (1.0 / 30 - i2 * (1.0 / 42 - i2 * (1.0 / 30 - i2 * (5.0 / 66 - i2 * (691.0 / 2730 - i2 * (7.0 / 6)))))));
+    return r + (inv + (0.5 * i2 + inv * series));
 }
 
 // d lg / d c of lg = log g, g ~ Gamma(c, 1), at a fixed uniform of the implicit form: -(dP(c, g) / dc) / (g p(g; c)), with the

@@ -44,7 +44,7 @@
 // Random numbers: ONE Philox block per (pixel, gamma, attempt).  Pixel `pixel` of object o has the 64-bit flat index
 // e = (first_object + o) * pix + pixel; the draws depend on (seed, draw, e) alone, so a batch cut into calls (or ranks) with
 // first_object draws what the whole batch draws.  kBetaTag = 0x42000000u (in use elsewhere: 0x544E48, 0x484D43, 0x4C000000 | ..,
-// 0x44000000 | .., 0).
+// 0x44000000 | .., 0x51000000 | .. -- beta_latent.hip's, which runs this sampler under its own fourth counter word --, 0).
 //
 // Layout and the order of the per-object sum: head.hip's, through quad_io.h -- one workgroup of 1024 threads per object, no atomics:
 //   quad q = pixels 4q .. 4q+3:  s_q = ((lp_4q + lp_4q+1) + lp_4q+2) + lp_4q+3                        (pixels past pix add +0.0f)

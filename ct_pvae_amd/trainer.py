@@ -41,6 +41,7 @@ from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
 from .latents import normal_latents
 from .marginals import PixelMarginals
 from .beta_head import beta_head
+from .beta_latents import beta_latents
 from .output_head import truncated_normal_head
 
 EPS32 = float(np.finfo(np.float32).eps)
@@ -283,7 +284,7 @@ def kl_normal_std(loc, scale):
 def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_decode, poisson_noise_multiplier, sqrt_reg,
                         kl_anneal, kl_multiplier, num_samples=2, theta=None, angles_i=None, pad=True, deterministic=False,
                         use_normal=True, model="rotate", noise="gaussian", fused_head=None, fused_latents=None,
-                        fused_beta_head=None):
+                        fused_beta_head=None, fused_beta_latents=None):
     """fused_head: None -- the output distribution is the chain of torch operations below, its uniforms from torch's global
     generator -- or (seed, draw, first_object): sample, log-density and its per-object sum come from ONE launch
     (output_head.truncated_normal_head, csrc/head.hip), the uniforms from Philox keyed by those three; --normal only.
@@ -294,7 +295,12 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     fused_beta_head: None, or (seed, draw, first_object): the DEFAULT Beta output head (use_normal=False) -- sample, clamp, log-density
     and its per-object sum -- comes from ONE launch (beta_head.beta_head, csrc/beta_head.hip), the draws from Philox keyed by those
     three, the gradient TensorFlow's implicit one.  Allowed with deterministic=True: the reference samples the output distribution
-    there too."""
+    there too.
+    fused_beta_latents: None -- the DEFAULT Beta latents and their KL term against Beta(0.5, 0.5) are the chain of torch operations
+    below, the draws from torch's global generator, the gradient torch's direct Beta derivative -- or (seed, draw, first_object): per
+    skip level ONE launch gives the ns samples and the per-object KL (beta_latents.beta_latents, csrc/beta_latent.hip), the draws from
+    Philox keyed by those three, the level and the sample, the gradient TensorFlow's implicit one; first_object is the offset of this
+    call's objects in the GLOBAL batch; use_normal=False only, not with deterministic."""
     if fused_head is not None and not use_normal:
         raise ValueError("fused_head is the TruncatedNormal output head: it needs use_normal=True (the Beta head is fused_beta_head)")
     if fused_beta_head is not None and use_normal:
@@ -302,10 +308,13 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
                          "TruncatedNormal: fused_head)")
     if fused_latents is not None and (not use_normal or deterministic):
         raise ValueError("fused_latents is the Normal latent block: it needs use_normal=True and deterministic=False (the Beta latents "
-                         "are not fused)")
+                         "are fused_beta_latents)")
+    if fused_beta_latents is not None and (use_normal or deterministic):
+        raise ValueError("fused_beta_latents is the Beta latent block: it needs use_normal=False and deterministic=False (the Normal "
+                         "latents are fused_latents)")
     skips = model_encode(input_encode / 300)
     q = None
-    if not deterministic and fused_latents is None:
+    if not deterministic and fused_latents is None and fused_beta_latents is None:
         q = []
         for sk in skips:
             loc, log_scale = sk.chunk(2, dim=1)
@@ -326,6 +335,14 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
         for level, sk in enumerate(skips):
             z, kl_level = normal_latents(sk.contiguous(), ns=ns, seed=seed, draw=draw, level=level, first_object=first_object,
                                          sqrt_reg=sqrt_reg)
+            q_sample.append(z)
+            level_kl.append(kl_level)
+    elif fused_beta_latents is not None:                            # :249-254, :267 in one launch per level
+        seed, draw, first_object = fused_beta_latents
+        q_sample, level_kl = [], []
+        for level, sk in enumerate(skips):                          # the input level's KL is unused (:325-327): it is not computed
+            z, kl_level = beta_latents(sk.contiguous(), ns=ns, seed=seed, draw=draw, level=level, first_object=first_object,
+                                       want_kl=level > 0)
             q_sample.append(z)
             level_kl.append(kl_level)
     elif use_normal:
@@ -365,7 +382,7 @@ def find_loss_vae_unsup(proj_sample, mask, input_encode, model_encode, model_dec
     recon = output_sample[(ns - 1) * B:]
     if deterministic:
         kl = lp.new_zeros(B)
-    elif fused_latents is not None:
+    elif fused_latents is not None or fused_beta_latents is not None:
         kl = sum(level_kl[2:], level_kl[1]) if len(level_kl) > 1 else lp.new_zeros(B)   # ascending level; the input level is unused
     elif use_normal:
         kl = sum(kl_normal_std(loc, scale).sum(dim=(1, 2, 3)) for loc, scale in q[1:])   # the input level is unused
@@ -398,6 +415,10 @@ _PIXEL_DIST_NEEDS = ("--pixel_dist samples the TruncatedNormal output head of sa
 
 
 _FUSED_BETA_HEAD_NEEDS = "--fused_beta_head is the default Beta output head: it cannot be combined with --normal (there: --fused_head)"
+_FUSED_LATENTS_NEEDS = ("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det (the default Beta "
+                        "latents: --fused_beta_latents)")
+_FUSED_BETA_LATENTS_NEEDS = ("--fused_beta_latents is the default Beta latent block: it cannot be combined with --normal (there: "
+                             "--fused_latents) or with --det")
 
 
 class PVAETrainer:
@@ -408,7 +429,9 @@ class PVAETrainer:
         if getattr(args, "fused_beta_head", False) and args.use_normal:
             raise ValueError(_FUSED_BETA_HEAD_NEEDS)
         if getattr(args, "fused_latents", False) and (not args.use_normal or args.deterministic):
-            raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
+            raise ValueError(_FUSED_LATENTS_NEEDS)
+        if getattr(args, "fused_beta_latents", False) and (args.use_normal or args.deterministic):
+            raise ValueError(_FUSED_BETA_LATENTS_NEEDS)
         if getattr(args, "pixel_dist", False) and (not args.use_normal or args.deterministic):
             raise ValueError(_PIXEL_DIST_NEEDS)
         self.world, self.rank, _ = sharding.env_world()
@@ -547,6 +570,9 @@ class PVAETrainer:
         fused_lat = None
         if getattr(a, "fused_latents", False):
             fused_lat = (a.head_seed, self.iter, sharding.shard_range(a.batch_size, self.rank, self.world)[0])   # _batch's lo
+        fused_beta_lat = None              # --fused_beta_latents: keyed exactly as --fused_latents
+        if getattr(a, "fused_beta_latents", False):
+            fused_beta_lat = (a.head_seed, self.iter, sharding.shard_range(a.batch_size, self.rank, self.world)[0])
         # --dp: seed = --head_seed, draw = the step index; the objects are counted as the head counts them (rank * B in the encoder,
         # rank * ns * B in the decoder's sample-major batch), so a run replays at its own world size.  The keys hold a draw only while
         # the training pass is built: every other caller of the networks (the evaluations, --pixel_dist) runs them without dropout.
@@ -560,7 +586,8 @@ class PVAETrainer:
                                                           theta=self.theta_host, angles_i=angles_i, pad=self.pad,
                                                           deterministic=a.deterministic, use_normal=a.use_normal,
                                                           model=getattr(a, "model", "rotate"), noise=getattr(a, "noise", "gaussian"),
-                                                          fused_head=fused, fused_latents=fused_lat, fused_beta_head=fused_beta)
+                                                          fused_head=fused, fused_latents=fused_lat, fused_beta_head=fused_beta,
+                                                          fused_beta_latents=fused_beta_lat)
         finally:
             if self.enc_drop is not None:
                 self.enc_drop.clear(), self.dec_drop.clear()
@@ -807,6 +834,11 @@ def get_args(argv=None):
                    help="sample the Normal latents and sum their KL term in one launch per skip level (csrc/latent.hip), with Philox "
                         "draws keyed by (--head_seed, step index, level, sample, global object) instead of torch's global generator; "
                         "needs --normal, not with --det")
+    p.add_argument("--fused_beta_latents", action="store_true",
+                   help="sample the default Beta latents and sum their KL term against Beta(0.5, 0.5) in one launch per skip level "
+                        "(csrc/beta_latent.hip), with Philox draws keyed by (--head_seed, step index, level, sample, global object) instead of "
+                        "torch's global generator and TensorFlow's implicit reparameterisation gradient instead of torch's direct Beta "
+                        "derivative; not with --normal, not with --det")
     p.add_argument("--fused_blocks", action="store_true",
                    help="the periodic pad in front of every ConvBlock's convolution and the maxout behind it as one launch each way "
                         "(csrc/convblock.hip) instead of chains of small torch launches; the same parameters, checkpoints and, with at most "
@@ -823,7 +855,7 @@ def get_args(argv=None):
     p.add_argument("--reproducible", action="store_true",
                    help="ask torch for deterministic convolution algorithms (torch.backends.cudnn.deterministic, process-wide): with "
                         "--fused_head two runs with equal seeds are then bit-equal; MIOpen's default weight gradients are not")
-    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's and --fused_beta_head's uniforms and of --fused_latents' draws")
+    p.add_argument("--head_seed", type=int, default=1234, help="seed of --fused_head's and --fused_beta_head's uniforms and of --fused_latents' and --fused_beta_latents' draws")
     p.add_argument("--random", action="store_true")
     p.add_argument("--save_path", default=None)
     p.add_argument("--restore", action="store_true", help="restore the latest checkpoint under --save_path before training / evaluating")
@@ -868,7 +900,9 @@ def get_args(argv=None):
     if args.fused_beta_head and args.use_normal:
         raise ValueError(_FUSED_BETA_HEAD_NEEDS)
     if args.fused_latents and (not args.use_normal or args.deterministic):
-        raise ValueError("--fused_latents is the Normal latent block: it needs --normal and cannot be combined with --det")
+        raise ValueError(_FUSED_LATENTS_NEEDS)
+    if args.fused_beta_latents and (args.use_normal or args.deterministic):
+        raise ValueError(_FUSED_BETA_LATENTS_NEEDS)
     if args.pixel_dist and (not args.use_normal or args.deterministic):
         raise ValueError(_PIXEL_DIST_NEEDS)
     if args.final_merit and (not args.save_path or args.no_final_eval):

@@ -790,6 +790,33 @@ int ctpvae_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, float s
 int ctpvae_latent_draws_host_f32(int n, int len, int ns, long long first_object, unsigned long long seed, unsigned draw, unsigned level,
                                  float *v_out_host);
 
+/* ---- the P-VAE's DEFAULT (Beta) latent block at one skip level (ctvae/helper_functions.py:249-254, :267, :325-327; backward
+ * compatible additions at ABI 3400): the ns reparameterised samples of Beta(pr(loc), pr(log_scale)), the KL term against the
+ * Beta(0.5, 0.5) prior and its per-object sum in ONE launch, their gradients in one more (csrc/beta_latent.hip states the function, the
+ * work split, the order of the sum and the backward's arithmetic).  skip_dev [B][2][len] as for ctpvae_latent_fwd_f32; there is no
+ * sqrt_reg.  a = pr(loc), b1 = pr(log_scale);
+ *   z[s * B + b][i] = 1 / (1 + exp(lg_1 - lg_0)), lg_j the log-space gammas of the Beta head's sampler (csrc/beta_head.hip);
+ *   kl[b][i] = ln pi - lbeta(a, b1) + (a - 1/2) psi(a) + (b1 - 1/2) psi(b1) + (1 - a - b1) psi(a + b1), float64 on the fp32 a, b1, rounded once.
+ * The draws of element i of object b, sample s, are words 0 .. 2 of the blocks
+ *   Philox4x32-10((lo32(e), hi32(e), draw, 0x51000000 | level << 16 | s << 5 | gamma << 4 | attempt), key = seed),  e = (first_object + b) * len + i,
+ * one block per (element, sample, gamma, attempt), attempt < 16.  Top bytes of the fourth counter word in use: 0x51 (here), 0x42 (the
+ * Beta head), 0x44 (dropout), 0x4C (the Normal latents); whole words 0x00544E48 (the TruncatedNormal head), 0x00484D43 (HMC), 0 (Poisson).
+ *   _fwd_f32: z_out_dev [ns * B][len]; kl_sum_out_dev [B] or NULL (the sum of an object's kl in the fixed order of csrc/beta_latent.hip:
+ *     the same bits whatever B and first_object), kl_elem_out_dev [B][len] or NULL -- with both NULL no KL is computed at all;
+ *     aux_out_dev [ns * B][len][2][4] or NULL: (zn, ub, attempt, lg) of the accepted attempt of each gamma (tests only).
+ *   _bwd_f32: g_skip_out_dev [B][2][len] for the cotangents g_z_dev [ns * B][len] and g_kl_dev [B] (either may be NULL: zero): the
+ *     implicit reparameterisation gradient of each gamma and the closed-form gradient of the KL term, float64, rounded once.  Nothing
+ *     is saved by the forward: the backward redraws.
+ *   _words_host_u32: the Philox words of one (level, s, gamma, attempt) into HOST memory out_host [n][len][4]; needs no GPU.
+ * ns * B * len <= 2^31 - 1; 1 <= ns <= 2048 (s < 2048); level <= 255; first_object >= 0. */
+int ctpvae_beta_latent_fwd_f32(const float *skip_dev, int B, int len, int ns, long long first_object, unsigned long long seed, unsigned draw,
+                               unsigned level, float *z_out_dev, float *kl_sum_out_dev, float *kl_elem_out_dev, float *aux_out_dev,
+                               ctpvae_stream_t stream);
+int ctpvae_beta_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, long long first_object, unsigned long long seed, unsigned draw,
+                               unsigned level, const float *g_z_dev, const float *g_kl_dev, float *g_skip_out_dev, ctpvae_stream_t stream);
+int ctpvae_beta_latent_words_host_u32(int n, int len, long long first_object, unsigned long long seed, unsigned draw, unsigned level, int s,
+                                      int gamma, int attempt, unsigned *out_host);
+
 /* ---- the glue around every convolution of the P-VAE's ConvBlock (ctvae/models.py:219-263, :330-341) as one launch each way
  * (csrc/convblock.hip states the functions and the backward's order of addition).  All tensors fp32, contiguous [N][C][H][W].
  * Periodic pad, planes = N * C, OH = H + hl + hr, OW = W + wl + wr (a pad may exceed the extent):
