@@ -169,6 +169,9 @@ SIGNATURES = {
     "ctpvae_tn_marginals_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
                                          _c_float, _c_float, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_tn_marginals_bin_host_f32": (_c_int, [_vp, ctypes.c_longlong, _c_float, _c_float, _c_int, _vp]),
+    "ctpvae_beta_marginals_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, ctypes.c_uint]),
+    "ctpvae_beta_marginals_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_uint,
+                                           _c_float, _c_float, _c_int, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_latent_fwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint,
                                        ctypes.c_uint, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_latent_bwd_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_float, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint,

@@ -1,8 +1,9 @@
-// beta_head.h -- what beta_head.hip (the Beta output head) shares with beta_latent.hip (the Beta latents) and the Beta kernel to come
-// (marginals): the layout of the
-// random numbers, the log-space gamma sampler, the pixel's function and the implicit reparameterisation gradient of a gamma's
-// logarithm.  beta_head.hip's header states the function; every file evaluates it through this code alone, so one
-// (alpha, beta, e, draw, seed) gives one x wherever it is computed (-ffp-contract=off: the same operations, the same bits).
+// beta_head.h -- what beta_head.hip (the Beta output head) shares with beta_latent.hip (the Beta latents) and beta_marginals.hip (the
+// per-pixel marginals of the head's samples): the layout of the random numbers, the log-space gamma sampler cut into the part that does
+// not depend on the random numbers (beta_gamma_prep, beta_prep) and the part that does (beta_gamma_draw, beta_draw), the pixel's
+// function and the implicit reparameterisation gradient of a gamma's logarithm.  beta_head.hip's header states the function; every
+// file evaluates it through this code alone, so one (alpha, beta, e, draw, seed) gives one x wherever it is computed
+// (-ffp-contract=off: the same operations, the same bits).
 #pragma once
 #include "tn_head.h"
 
@@ -25,18 +26,35 @@ __host__ __device__ inline unsigned beta_latent_word3(unsigned level, unsigned s
     return kBetaLatentTag | (level << 16) | (s << 5) | (gamma << 4);
 }
 
-// log of a Gamma(c, 1) sample: the accepted attempt's normal and boost uniform, its index, and lg = log(d) + log(v) + boost.  word3 is
-// the fourth counter word WITHOUT the attempt (the head: kBetaTag | gamma << 8; the latents: beta_latent_word3); attempt k is ORed in here.
+// log of a Gamma(c, 1) sample: the accepted attempt's normal and boost uniform, its index, and lg = log(d) + log(v) + boost
 struct BetaGamma {
     float zn, ub, lg;
     int k;
 };
 
-__device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long e, unsigned draw, unsigned word3, unsigned k0, unsigned k1)
+// a gamma before its random numbers: the concentration c, Marsaglia-Tsang's d = cb - 1/3 (cb = c below 1 boosted by one), s = 1 /
+// sqrt(9 d) and log(d)
+struct BetaGammaPrep {
+    float c, d, s, logd;
+};
+
+__device__ __forceinline__ BetaGammaPrep beta_gamma_prep(float c)
 {
+    BetaGammaPrep p;
     const float cb = c < 1.0f ? c + 1.0f : c;
-    const float d = cb - kBetaThird;
-    const float s = 1.0f / sqrtf(9.0f * d);
+    p.c = c;
+    p.d = cb - kBetaThird;
+    p.s = 1.0f / sqrtf(9.0f * p.d);
+    p.logd = logf(p.d);
+    return p;
+}
+
+// the attempt loop, log(v) and the boost.  word3 is the fourth counter word WITHOUT the attempt (the head: kBetaTag | gamma << 8; the
+// latents: beta_latent_word3); attempt k is ORed in here.
+__device__ __forceinline__ BetaGamma beta_gamma_draw(const BetaGammaPrep &p, unsigned long long e, unsigned draw, unsigned word3, unsigned k0,
+                                                     unsigned k1)
+{
+    const float c = p.c, d = p.d, s = p.s;
     BetaGamma r{0.0f, 0.5f, 0.0f, kBetaAttempts - 1};
     float v = 1.0f;
 #pragma unroll 1
@@ -50,7 +68,47 @@ __device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long 
         if (w > 0.0f && logf(ua) < ((0.5f * (zn * zn) + d) - d * v3) + d * logf(v3)) break;
     }
     const float boost = c < 1.0f ? logf(r.ub) / c : 0.0f;
-    r.lg = (logf(d) + logf(v)) + boost;
+    r.lg = (p.logd + logf(v)) + boost;
+    return r;
+}
+
+// prep and draw in one: a gamma whose concentration is used once (the latents)
+__device__ __forceinline__ BetaGamma beta_log_gamma(float c, unsigned long long e, unsigned draw, unsigned word3, unsigned k0, unsigned k1)
+{
+    return beta_gamma_draw(beta_gamma_prep(c), e, draw, word3, k0, k1);
+}
+
+// the pixel before its random numbers: a = pr(alpha), b = pr(beta), their slopes, and the two gammas' preps
+struct BetaPrep {
+    float a, b, da, db;
+    BetaGammaPrep g0, g1;
+};
+
+__device__ __forceinline__ BetaPrep beta_prep(float alpha, float beta)
+{
+    BetaPrep r;
+    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
+    r.a = alpha >= 1.0f ? alpha : ea + kHeadEps;
+    r.b = beta >= 1.0f ? beta : eb + kHeadEps;
+    r.da = alpha >= 1.0f ? 1.0f : ea;
+    r.db = beta >= 1.0f ? 1.0f : eb;
+    r.g0 = beta_gamma_prep(r.a);
+    r.g1 = beta_gamma_prep(r.b);
+    return r;
+}
+
+// the pixel's sample for (e, draw, seed): the head's two gammas and x = 1 / (1 + exp(lg_1 - lg_0)), not clamped
+struct BetaDraw {
+    BetaGamma g0, g1;
+    float x;
+};
+
+__device__ __forceinline__ BetaDraw beta_draw(const BetaPrep &pr, unsigned long long e, unsigned draw, unsigned k0, unsigned k1)
+{
+    BetaDraw r;
+    r.g0 = beta_gamma_draw(pr.g0, e, draw, kBetaTag | (0u << 8), k0, k1);
+    r.g1 = beta_gamma_draw(pr.g1, e, draw, kBetaTag | (1u << 8), k0, k1);
+    r.x = 1.0f / (1.0f + expf(r.g1.lg - r.g0.lg));
     return r;
 }
 
@@ -65,15 +123,12 @@ template <bool BWD>
 __device__ __forceinline__ BetaPixel beta_pixel(float alpha, float beta, unsigned long long e, unsigned draw, unsigned k0, unsigned k1,
                                                 float sr)
 {
+    const BetaPrep pr = beta_prep(alpha, beta);
+    const BetaDraw dr = beta_draw(pr, e, draw, k0, k1);
     BetaPixel r;
-    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
-    r.a = alpha >= 1.0f ? alpha : ea + kHeadEps;
-    r.b = beta >= 1.0f ? beta : eb + kHeadEps;
-    r.da = alpha >= 1.0f ? 1.0f : ea;
-    r.db = beta >= 1.0f ? 1.0f : eb;
-    r.g0 = beta_log_gamma(r.a, e, draw, kBetaTag | (0u << 8), k0, k1);
-    r.g1 = beta_log_gamma(r.b, e, draw, kBetaTag | (1u << 8), k0, k1);
-    r.x = 1.0f / (1.0f + expf(r.g1.lg - r.g0.lg));
+    r.a = pr.a, r.b = pr.b, r.da = pr.da, r.db = pr.db;
+    r.g0 = dr.g0, r.g1 = dr.g1;
+    r.x = dr.x;
     r.y = 1.0f / (1.0f + expf(r.g0.lg - r.g1.lg));
     // the upper bound is tested on y: x > hi <=> y < 1 - hi, and next to 1 y keeps the relative accuracy that x has lost
     const float hi = 1.0f - sr, lo_y = 1.0f - hi;

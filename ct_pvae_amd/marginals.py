@@ -1,11 +1,14 @@
-"""Per-pixel posterior marginals of the P-VAE's TruncatedNormal output head (the reference's CT_VAE.pixel_dist): a histogram and two
-moments per pixel, accumulated on the device with no sample ever written to memory (csrc/marginals.hip states the layout, the bin rule
-and the fixed order of the float64 sums).
+"""Per-pixel posterior marginals of the P-VAE's output head (the reference's CT_VAE.pixel_dist) -- the TruncatedNormal head of --normal
+or the reference's default Beta head --: a histogram and two moments per pixel, accumulated on the device with no sample ever written to
+memory (csrc/marginals.hip states the layout, the bin rule and the fixed order of the float64 sums; csrc/beta_marginals.hip runs the
+same code on the Beta head's samples).
 
     m = PixelMarginals((X, Y), bins=50, lo=0.005, width=0.01, device="cuda")    the reference's np.arange(0.005, 0.51, 0.01)
     m.add(alpha, beta, draws=100, seed=1234, draw0=0, first_object=0)           alpha, beta [n][1][X][Y]: n * draws samples per pixel,
                                                                                 sample (o, pixel, k) IS truncated_normal_head's x
                                                                                 for draw = draw0 + k
+    m = PixelMarginals((X, Y), head="beta")                                     the same of the default Beta head: sample (o, pixel, k)
+                                                                                IS beta_head's x for draw = draw0 + k
     m.count, m.hist, m.mean(), m.std(), m.edges, m.save(path), PixelMarginals.load(path)
     bin_samples(samples, lo, width, bins)                                       the same bin rule on any [..., pix] host array (e.g.
                                                                                 hmc_sample's output), so two curves share their bins
@@ -24,6 +27,7 @@ from .output_head import _counter_args
 __all__ = ["PixelMarginals", "bin_samples", "bin_columns", "MAX_BINS"]
 
 MAX_BINS = 254     # CTPVAE_MARGINALS_MAX_BINS
+HEADS = {"truncated_normal": "tn_marginals", "beta": "beta_marginals"}     # head -> the stem of its two entry points
 
 
 def _grid_args(bins, lo, width):
@@ -76,9 +80,13 @@ def _check_input(name, t, shape_xy):
 
 class PixelMarginals:
     """State of the per-pixel marginals of an (X, Y) pixel grid: hist [X * Y][bins + 2] int64, s1, s2 [X * Y] float64 and a count, all
-    zero at first; add() accumulates into them on the device."""
+    zero at first; add() accumulates into them on the device.  head: "truncated_normal" (the output head of --normal) or "beta" (the
+    reference's default output head) -- whose samples add() draws."""
 
-    def __init__(self, shape, bins=50, lo=0.005, width=0.01, device="cuda"):
+    def __init__(self, shape, bins=50, lo=0.005, width=0.01, device="cuda", head="truncated_normal"):
+        if head not in HEADS:
+            raise ValueError(f"PixelMarginals: head must be one of {sorted(HEADS)} (got {head!r})")
+        self.head = head
         X, Y = (int(v) for v in shape)
         if X < 1 or Y < 1:
             raise ValueError(f"PixelMarginals: the pixel grid must be (X, Y) with both >= 1 (got {tuple(shape)})")
@@ -93,7 +101,9 @@ class PixelMarginals:
     def add(self, alpha, beta, *, draws, seed, draw0=0, first_object=0):
         """Add the n * draws samples per pixel of alpha, beta [n][1][X][Y] (contiguous float32 tensors on the state's device; detached,
         no autograd): sample (o, pixel, k) is truncated_normal_head(alpha, beta, seed=seed, draw=draw0 + k, first_object=first_object).x
-        of object o at that pixel, bit for bit.  Every check is made before anything is launched."""
+        of object o at that pixel, bit for bit; with head="beta" it is beta_head(alpha, beta, seed=seed, draw=draw0 + k,
+        first_object=first_object)[0] (the sample is not clamped: sqrt_reg plays no part in it).  Every check is made before anything
+        is launched."""
         _check_input("alpha", alpha, self.shape)
         _check_input("beta", beta, self.shape)
         if beta.shape != alpha.shape:
@@ -113,12 +123,13 @@ class PixelMarginals:
                                          f"alpha on {alpha.device}, beta on {beta.device}); there is no CPU path")
         a, b = alpha.detach(), beta.detach()
         lib = _lib.load()
-        ws_bytes = _lib.check(lib.ctpvae_tn_marginals_workspace_bytes(n, pix, draws), "tn_marginals_workspace_bytes")
+        stem = HEADS[self.head]
+        ws_bytes = _lib.check(getattr(lib, f"ctpvae_{stem}_workspace_bytes")(n, pix, draws), f"{stem}_workspace_bytes")
         with torch.cuda.device(self.device):
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=self.device)
-            _lib.check(lib.ctpvae_tn_marginals_f32(a.data_ptr(), b.data_ptr(), n, pix, first_object, seed, draw0, draws, self.lo, self.width,
-                                                   self.bins, self._hist.data_ptr(), self._s1.data_ptr(), self._s2.data_ptr(),
-                                                   ws.data_ptr(), _stream_ptr()), "tn_marginals")
+            _lib.check(getattr(lib, f"ctpvae_{stem}_f32")(a.data_ptr(), b.data_ptr(), n, pix, first_object, seed, draw0, draws, self.lo,
+                                                          self.width, self.bins, self._hist.data_ptr(), self._s1.data_ptr(),
+                                                          self._s2.data_ptr(), ws.data_ptr(), _stream_ptr()), stem)
         self.count += n * draws
         return self
 
@@ -154,15 +165,19 @@ class PixelMarginals:
         return var.clamp_min(0.0).sqrt().view(self.shape)
 
     def save(self, path):
-        """One .npz: hist, s1, s2, count, lo, width (and the grid's shape)."""
+        """One .npz: hist, s1, s2, count, lo, width, head (a plain numpy string) and the grid's shape."""
         np.savez(path, hist=self._hist.cpu().numpy(), s1=self._s1.cpu().numpy(), s2=self._s2.cpu().numpy(), count=np.int64(self.count),
-                 lo=np.float64(self.lo), width=np.float64(self.width), shape=np.asarray(self.shape, np.int64))
+                 lo=np.float64(self.lo), width=np.float64(self.width), shape=np.asarray(self.shape, np.int64),
+                 head=np.str_(self.head))
 
     @classmethod
     def load(cls, path, device="cuda"):
+        """The state save() wrote; a file without `head` (written before there were two) is a TruncatedNormal state."""
         with np.load(path) as f:
             hist = f["hist"]
-            m = cls(tuple(int(v) for v in f["shape"]), bins=hist.shape[1] - 2, lo=float(f["lo"]), width=float(f["width"]), device=device)
+            head = str(f["head"]) if "head" in f.files else "truncated_normal"
+            m = cls(tuple(int(v) for v in f["shape"]), bins=hist.shape[1] - 2, lo=float(f["lo"]), width=float(f["width"]), device=device,
+                    head=head)
             if hist.shape[0] != m.shape[0] * m.shape[1]:
                 raise ValueError(f"{path}: hist has {hist.shape[0]} rows for a grid of {m.shape}")
             m._hist.copy_(torch.from_numpy(hist))

@@ -410,8 +410,17 @@ class AngleStream:
         return out
 
 
-_PIXEL_DIST_NEEDS = ("--pixel_dist samples the TruncatedNormal output head of sampled Normal latents: it needs --normal and cannot be "
-                     "combined with --det (there are no marginals of the Beta head)")
+_PIXEL_DIST_NEEDS = ("--pixel_dist adds the keyed samples of a fused output head over sampled latents: it needs --normal (the "
+                     "TruncatedNormal head's marginals) or --fused_beta_head (the default Beta head's: the marginals are that keyed head's "
+                     "samples, there are none of torch's generator's) and cannot be combined with --det")
+
+
+def _pixel_dist_head(args):
+    """The one rule of --pixel_dist (get_args, PVAETrainer and pixel_dist apply it): the PixelMarginals head of these arguments --
+    "truncated_normal" with --normal, "beta" with --fused_beta_head and no --normal -- or a ValueError; never with --det."""
+    if args.deterministic or not (args.use_normal or getattr(args, "fused_beta_head", False)):
+        raise ValueError(_PIXEL_DIST_NEEDS)
+    return "truncated_normal" if args.use_normal else "beta"
 
 
 _FUSED_BETA_HEAD_NEEDS = "--fused_beta_head is the default Beta output head: it cannot be combined with --normal (there: --fused_head)"
@@ -432,8 +441,8 @@ class PVAETrainer:
             raise ValueError(_FUSED_LATENTS_NEEDS)
         if getattr(args, "fused_beta_latents", False) and (args.use_normal or args.deterministic):
             raise ValueError(_FUSED_BETA_LATENTS_NEEDS)
-        if getattr(args, "pixel_dist", False) and (not args.use_normal or args.deterministic):
-            raise ValueError(_PIXEL_DIST_NEEDS)
+        if getattr(args, "pixel_dist", False):
+            _pixel_dist_head(args)
         self.world, self.rank, _ = sharding.env_world()
         self.sqrt_reg = EPS32
         # the nets' shapes are static: --miopen_find lets MIOpen search its convolution algorithms once (14.9 -> 11.5 ms
@@ -745,12 +754,13 @@ class PVAETrainer:
         samples per copy, decodes them and adds num_samples_1 draws of the output head per decoder output to a PixelMarginals
         (seed = --head_seed, draws r * num_samples_1 ..): num_repeats * ns * b * num_samples_1 samples per pixel, none of them stored.
         With --fused_latents the latents are normal_latents' keyed by (--head_seed, draw = r); without it they come from torch's
-        global generator as in find_loss_vae_unsup.  The encoder does not depend on r and runs once; the projector and the likelihood,
-        which the reference computes and discards, are not called.  Only rank 0 runs it: it writes <save_path>/pixel_dist_<en>.npz,
-        prints one line and returns the PixelMarginals (the other ranks return None)."""
+        global generator as in find_loss_vae_unsup.  Without --normal (with --fused_beta_head) the state is PixelMarginals(head="beta"):
+        the samples are beta_head's, the latents beta_latents' keyed the same way with --fused_beta_latents and otherwise
+        Beta(pr(loc), pr(log_scale)).sample((ns,)) from torch's generator, sample-major.  The encoder does not depend on r and runs
+        once; the projector and the likelihood, which the reference computes and discards, are not called.  Only rank 0 runs it: it
+        writes <save_path>/pixel_dist_<en>.npz, prints one line and returns the PixelMarginals (the other ranks return None)."""
         a = self.args
-        if not a.use_normal or a.deterministic:
-            raise ValueError(_PIXEL_DIST_NEEDS)
+        head = _pixel_dist_head(a)
         example_num, num_repeats = int(example_num), int(num_repeats)
         if not 0 <= example_num < self.input_encode.shape[0]:
             raise ValueError(f"pixel_dist: example {example_num} is not one of the {self.input_encode.shape[0]} examples")
@@ -759,20 +769,28 @@ class PVAETrainer:
         if self.rank != 0:
             return None
         ns, B = int(a.ns), a.batch_size
-        fused = bool(getattr(a, "fused_latents", False))
+        fused = bool(getattr(a, "fused_latents" if head == "truncated_normal" else "fused_beta_latents", False))
         skips = self.enc(self.input_encode[example_num:example_num + 1].repeat(B, 1, 1, 1) / 300)
         if fused:
             skips = [sk.contiguous() for sk in skips]
-        else:
+        elif head == "truncated_normal":
             q = [(loc.repeat(ns, 1, 1, 1), (positive_range(log_scale) + self.sqrt_reg).repeat(ns, 1, 1, 1))
                  for loc, log_scale in (sk.chunk(2, dim=1) for sk in skips)]
-        m = PixelMarginals((self.x_size, self.y_size), bins=bins, lo=lo, width=width, device=self.dev)
+        else:
+            q = [torch.distributions.Beta(positive_range(loc), positive_range(log_scale))
+                 for loc, log_scale in (sk.chunk(2, dim=1) for sk in skips)]
+        m = PixelMarginals((self.x_size, self.y_size), bins=bins, lo=lo, width=width, device=self.dev, head=head)
         for r in range(num_repeats):
-            if fused:
+            if fused and head == "truncated_normal":
                 q_sample = [normal_latents(sk, ns=ns, seed=a.head_seed, draw=r, level=level, first_object=0, sqrt_reg=self.sqrt_reg)[0]
                             for level, sk in enumerate(skips)]
-            else:
+            elif fused:
+                q_sample = [beta_latents(sk, ns=ns, seed=a.head_seed, draw=r, level=level, first_object=0, want_kl=False)[0]
+                            for level, sk in enumerate(skips)]
+            elif head == "truncated_normal":
                 q_sample = [loc + scale * torch.randn_like(loc) for loc, scale in q]
+            else:                                                       # sample-major, as in find_loss_vae_unsup
+                q_sample = [d.sample((ns,)).reshape((ns * B,) + tuple(d.concentration1.shape[1:])) for d in q]
             alpha, beta = self.dec(q_sample)
             m.add(alpha.contiguous(), beta.contiguous(), draws=num_samples_1, seed=a.head_seed, draw0=r * num_samples_1)
         if save_path is not None:
@@ -876,7 +894,8 @@ def get_args(argv=None):
     p.add_argument("--pixel_dist", action="store_true",
                    help="per-pixel marginals of the network's posterior for example --en (ctvae/main_ct_vae.py:103, CT_VAE.pixel_dist): "
                         "a histogram and two moments per pixel over --pixel_repeats decoder passes of 100 draws each, written to "
-                        "<save_path>/pixel_dist_<en>.npz (csrc/marginals.hip; no sample is stored); needs --normal, not with --det")
+                        "<save_path>/pixel_dist_<en>.npz (csrc/marginals.hip, csrc/beta_marginals.hip; no sample is stored); needs --normal "
+                        "(the TruncatedNormal head's marginals) or --fused_beta_head (the default Beta head's), not with --det")
     p.add_argument("--en", type=int, dest="example_num", default=0, help="the example --pixel_dist looks at")
     p.add_argument("--pixel_repeats", type=int, default=10000,
                    help="decoder passes of --pixel_dist, each over -b copies of the example and --ns latent samples (the reference's "
@@ -903,8 +922,8 @@ def get_args(argv=None):
         raise ValueError(_FUSED_LATENTS_NEEDS)
     if args.fused_beta_latents and (args.use_normal or args.deterministic):
         raise ValueError(_FUSED_BETA_LATENTS_NEEDS)
-    if args.pixel_dist and (not args.use_normal or args.deterministic):
-        raise ValueError(_PIXEL_DIST_NEEDS)
+    if args.pixel_dist:
+        _pixel_dist_head(args)
     if args.final_merit and (not args.save_path or args.no_final_eval):
         raise ValueError("--final_merit scores the final evaluation's reconstruction_final.npy: it needs --save_path and cannot be "
                          "combined with --no_final_eval")

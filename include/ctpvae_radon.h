@@ -764,6 +764,18 @@ int ctpvae_tn_marginals_f32(const float *alpha_dev, const float *beta_dev, int n
                             long long *hist_dev, double *s1_dev, double *s2_dev, void *workspace_dev, ctpvae_stream_t stream);
 int ctpvae_tn_marginals_bin_host_f32(const float *x_host, long long count, float lo, float width, int bins, int *col_out_host);
 
+/* ---- per-pixel marginals of the Beta output head, the reference's default output distribution (backward compatible additions at
+ * ABI 3400; csrc/beta_marginals.hip): ctpvae_tn_marginals_f32 with the other head's samples.  alpha_dev, beta_dev [n][pix] as for
+ * ctpvae_beta_head_fwd_f32; sample (o, pixel, k), k < draws, IS, bit for bit, the x that ctpvae_beta_head_fwd_f32 writes for that object
+ * and pixel with draw = draw0 + k and the same seed and first_object (x is not clamped: sqrt_reg plays no part in it).  A NaN alpha or
+ * beta gives NaN samples for that pixel: they count in column 0 and make its s1, s2 NaN; no other pixel is touched.  The state, the bin
+ * rule (on the host: ctpvae_tn_marginals_bin_host_f32, which does not depend on the head), the workspace rule, the order of the float64
+ * sums, the argument rules and the refusals are ctpvae_tn_marginals_f32's; every check is made before any launch. */
+long long ctpvae_beta_marginals_workspace_bytes(int n, int pix, unsigned draws);
+int ctpvae_beta_marginals_f32(const float *alpha_dev, const float *beta_dev, int n, int pix, long long first_object,
+                              unsigned long long seed, unsigned draw0, unsigned draws, float lo, float width, int bins,
+                              long long *hist_dev, double *s1_dev, double *s2_dev, void *workspace_dev, ctpvae_stream_t stream);
+
 /* ---- the P-VAE's Normal latent block at one skip level (ctvae/helper_functions.py:247-252, :267, :325-327): the ns reparameterised
  * samples, the KL term against N(0, 1) and its per-object sum in ONE launch, their gradients in one more (csrc/latent.hip states the
  * function, the order of the sum and the layout of the random numbers).  skip_dev [B][2][len]: the encoder's output at the level,
