@@ -18,5 +18,6 @@ from .latents import latent_draws, normal_latents  # noqa: F401
 from .marginals import PixelMarginals, bin_samples  # noqa: F401
 from .convblock import dropout, dropout_mask, dropout_pad, maxout, periodic_pad  # noqa: F401
 from .merit import image_merits  # noqa: F401
+from .update import FusedUpdate, adam_alpha  # noqa: F401
 
 __version__ = "0.2.0"

@@ -202,6 +202,11 @@ SIGNATURES = {
     "ctpvae_merit_workspace_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "ctpvae_merit_f32": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
     "ctpvae_merit_f64": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ctpvae_update_chunk_len": (_c_int, []),
+    "ctpvae_update_plan_bytes": (ctypes.c_longlong, [_vp, _c_int]),
+    "ctpvae_update_plan_host": (_c_int, [_vp, _vp, _c_int, _vp]),
+    "ctpvae_update_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float,
+                                   _c_float, _vp]),
 }
 
 _lib = None

@@ -12,7 +12,9 @@ caller of the projector -- runs on the hand-written kernels.  What is reproduced
     pnm * factor**iter with factor = exp(log(pnm/pnm_start)/num_iter) (ctvae/main_ct_vae.py:146-149, :392 -- the
     variable already holds the FINAL pnm, so the effective multiplier runs pnm .. pnm^2/pnm_start; kept as is)
   * loss = mean over the batch / 1e5 (:478); NaN gradients zeroed, per-tensor clip_by_norm(100), Adam(1e-4, eps 1e-7)
-    (:353, :482-485); encoder input scaled by 1/300 (ctvae/helper_functions.py:239)
+    (:353, :482-485); encoder input scaled by 1/300 (ctvae/helper_functions.py:239).  By default the Adam is torch's, whose epsilon
+    stands INSIDE the bias correction (Keras's stands outside: with --ae 1e-7 the reference's acts as 3.2e-6 in torch's terms at the
+    first step) and the clip multiplies by min(1, norm / l2); --fused_update runs the reference's own arithmetic (csrc/update.hip)
   * NaN loss stops the run (:401-402); checkpoint every save_interval and at the end (:409-415)
 
 Data parallelism is new (the reference is single-device): every rank trains on its shard of the batch and the flat
@@ -43,6 +45,7 @@ from .marginals import PixelMarginals
 from .beta_head import beta_head
 from .beta_latents import beta_latents
 from .output_head import truncated_normal_head
+from .update import FusedUpdate
 
 EPS32 = float(np.finfo(np.float32).eps)
 
@@ -482,6 +485,9 @@ class PVAETrainer:
         # fused: the whole Adam update in one multi-tensor launch on the device (the default foreach form is ~10)
         self.opt = torch.optim.Adam(self.params + ([self.pnm] if a.train_pnm else []), lr=a.lr, eps=a.adam_epsilon,
                                     fused=(device.type == "cuda") and os.environ.get("CTPVAE_ADAM_FUSED", "1") == "1")
+        # --fused_update: the update stage is update.FusedUpdate (csrc/update.hip) over the parameters that get a gradient, built at the first
+        # step (or from a restored checkpoint's entries); self.opt then only holds the parameter list and the group's settings
+        self.upd = None
         self.kl_anneal = 1.0
         self.angles = AngleStream(self.num_angles, a.api, seed=7)     # same stream on every rank
         self.iter = 0
@@ -617,6 +623,11 @@ class PVAETrainer:
         if self._bucket is None or not self._bucket.matches(grads):
             self._bucket = sharding.FlatGradBucket(grads)
         bucket = self._bucket.fill(grads).allreduce_(average=False)
+        if getattr(a, "fused_update", False):
+            # the reference's own arithmetic (Keras's epsilon placement, tf.clip_by_norm's form) in two launches with a stated order of
+            # the norms' sums: the bucket is read only, p.grad is not pointed at it and self.opt takes no step
+            self._fused_update(with_grad).step(bucket.flat)
+            return loss.detach()
         # tf.where(is_nan, 0, grad), then tf.clip_by_norm(g, norm) per tensor (ctvae/main_ct_vae.py:482-484) -- in one
         # flat buffer and a handful of multi-tensor launches, with no host round trip (a Python `if norm > clip` per
         # tensor would synchronise 76 times a step)
@@ -627,6 +638,35 @@ class PVAETrainer:
         bucket.attach(with_grad)
         self.opt.step()
         return loss.detach()
+
+    def _fused_update(self, with_grad):
+        """--fused_update's FusedUpdate over exactly the parameters that got a gradient this step (--train_pnm's scalar among them: a
+        tensor of one element).  Should the set change between steps, the moments move over through the state dictionary."""
+        a = self.args
+        if self.upd is None or not self.upd.same_params(with_grad):
+            state = self.optimizer_state() if self.upd is not None else None
+            self.upd = FusedUpdate(with_grad, lr=a.lr, eps=a.adam_epsilon, clip_norm=a.norm)
+            if state is not None:
+                self._load_fused_update(state, with_grad)
+        return self.upd
+
+    def _load_fused_update(self, state, params):
+        """Load the entries of `params` from a state dictionary laid out over self.opt's whole parameter list."""
+        index = {id(p): i for i, p in enumerate(self.opt.param_groups[0]["params"])}
+        rows = [index[id(p)] for p in params]
+        self.upd.load_state_dict({"state": {k: state["state"][i] for k, i in enumerate(rows) if i in state["state"]},
+                                  "param_groups": [dict(state["param_groups"][0], params=list(range(len(rows))))]})
+
+    def optimizer_state(self):
+        """The optimiser's state dictionary in torch.optim.Adam's layout over self.opt's parameter list -- with --fused_update taken
+        from the FusedUpdate (step, exp_avg = m, exp_avg_sq = v of the parameters it updates), so that a checkpoint written with the
+        flag restores without it and the other way round."""
+        if not getattr(self.args, "fused_update", False) or self.upd is None:
+            return self.opt.state_dict()
+        index = {id(p): i for i, p in enumerate(self.opt.param_groups[0]["params"])}
+        own = self.upd.state_dict()
+        group = dict(self.opt.state_dict()["param_groups"][0], lr=self.upd.lr, betas=(self.upd.beta1, self.upd.beta2), eps=self.upd.eps)
+        return {"state": {index[id(p)]: own["state"][k] for k, p in enumerate(self.upd.params) if k in own["state"]}, "param_groups": [group]}
 
     def train_step(self, sync=True):
         """One optimisation step.  sync=True returns the loss as a python float (a host round trip, as the reference's
@@ -665,7 +705,7 @@ class PVAETrainer:
 
     def save(self, path, losses):
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        torch.save({"enc": self.enc.state_dict(), "dec": self.dec.state_dict(), "opt": self.opt.state_dict(),
+        torch.save({"enc": self.enc.state_dict(), "dec": self.dec.state_dict(), "opt": self.optimizer_state(),
                     "kl_anneal": self.kl_anneal, "pnm": self.pnm.detach().cpu(), "iter": self.iter, "losses": losses}, path)
 
     def latest_checkpoint(self):
@@ -680,7 +720,18 @@ class PVAETrainer:
         ck = torch.load(path, map_location=self.dev)
         self.enc.load_state_dict(ck["enc"])
         self.dec.load_state_dict(ck["dec"])
-        self.opt.load_state_dict(ck["opt"])
+        if getattr(self.args, "fused_update", False):
+            # the checkpoint's entries are the parameters its run updated: the FusedUpdate is built over them (none yet: at the first step)
+            full = self.opt.param_groups[0]["params"]
+            if len(ck["opt"]["param_groups"]) != 1 or len(ck["opt"]["param_groups"][0]["params"]) != len(full):
+                raise ValueError("loaded state dict contains a parameter group that doesn't match the size of optimizer's group")
+            rows = sorted(ck["opt"]["state"])
+            self.upd = None
+            if rows:
+                self.upd = FusedUpdate([full[i] for i in rows], lr=self.args.lr, eps=self.args.adam_epsilon, clip_norm=self.args.norm)
+                self._load_fused_update(ck["opt"], self.upd.params)
+        else:
+            self.opt.load_state_dict(ck["opt"])
         self.kl_anneal, self.iter = ck["kl_anneal"], ck["iter"]      # (iter is also --fused_head's draw index)
         with torch.no_grad():
             self.pnm.copy_(ck["pnm"].to(self.dev))
@@ -863,6 +914,12 @@ def get_args(argv=None):
                         "two copies of a pixel per axis, the same values; independent of --normal and --det.  Measured at the c3 recipe "
                         "(profiles/convblock_timing.txt): alone NOT measurably faster (173.8 against 173.1 steps/s, the windows overlap); "
                         "with --fused_head --fused_latents 248.1 against 237.6 steps/s, the windows overlap too")
+    p.add_argument("--fused_update", action="store_true",
+                   help="the update stage -- NaN filter, per-tensor clip_by_norm (--norm), Adam (--lr, --ae) -- as two launches over the flat "
+                        "gradient bucket (csrc/update.hip) instead of torch's chain and torch.optim.Adam: Keras's Adam, as the reference runs "
+                        "it (epsilon outside the bias correction: with --ae 1e-7 it acts as 3.2e-6 in torch's terms at the first step), "
+                        "tf.clip_by_norm's own form, and the norms' sums of squares in float64 in a stated order; the checkpoint's optimiser "
+                        "entry keeps torch.optim.Adam's layout, so it restores with or without the flag; independent of every other flag")
     p.add_argument("--dp", type=_dropout_prob, dest="dropout_prob", default=0.0,
                    help="dropout probability of every ConvBlock's input (ctvae/main_ct_vae.py:41-42, ctvae/models.py:283-284), 0 <= p < 1; "
                         "0 (the default): no dropout, the networks and their launches as without the flag.  The masks are Philox-keyed by "

@@ -899,6 +899,28 @@ int ctpvae_merit_f32(const float *ref_dev, const float *test_dev, int n, int X, 
 int ctpvae_merit_f64(const double *ref_dev, const double *test_dev, int n, int X, int Y, void *workspace_dev, double *out_dev,
                      ctpvae_stream_t stream);
 
+/* ---- the update stage of a P-VAE training step (ctvae/main_ct_vae.py:353, :482-485): tf.where(is_nan, 0, g), tf.clip_by_norm per
+ * tensor and Keras's Adam (epsilon outside the bias correction) as TWO launches over the flat gradient buffer, whatever the number of
+ * tensors; csrc/update.hip states every operation, the order of the float64 sum of squares and the two deviations from TensorFlow.
+ * Added without a new ABI version: nothing that existed changes.  T tensors of lens_host[k] >= 1 elements lie back to back in
+ * grad_dev / m_dev / v_dev (float32, 4-byte aligned, any offsets); the parameters stay where they are, params_host[k] is tensor k's
+ * DEVICE address (4-byte aligned), held in host memory.
+ *   _chunk_len: C, the longest chunk (host only).
+ *   _plan_bytes: bytes of the chunk table for these lengths = 32 * the number of chunks, sum of ceil(len / C) (host only).
+ *   _plan_host: the table into HOST memory plan_out_host (8-byte aligned): per chunk {int64 flat offset, address of the parameter's
+ *     element there, int32 length, tensor, index of the tensor's first chunk, chunks of the tensor}; tensor after tensor, ascending in
+ *     offset, no chunk across a tensor boundary or longer than C.  The caller copies it to the device.
+ *   _update_f32: launch 1 writes one float64 per chunk into partials_dev [n_chunks]; launch 2 adds each tensor's partials in ascending
+ *     order, stores l2 = (float)sqrt(sum) into norms_out_dev [T] and updates m_dev, v_dev and the parameters in place; grad_dev is read
+ *     only (it keeps its NaNs).  t >= 1 is the step this call takes (for the record: the device keeps no counter), alpha the caller's
+ *     float32(lr * sqrt(1 - beta2^t) / (1 - beta1^t)) evaluated in float64; clip > 0; 0 <= b1, b2 < 1; eps >= 0.  plan_dev must be the
+ *     table _plan_host built for exactly these buffers: the kernels trust it.  No synchronisation, nothing read back. */
+int ctpvae_update_chunk_len(void);
+long long ctpvae_update_plan_bytes(const long long *lens_host, int T);
+int ctpvae_update_plan_host(const long long *lens_host, const void *const *params_host, int T, void *plan_out_host);
+int ctpvae_update_f32(const void *plan_dev, int n_chunks, int T, const float *grad_dev, float *m_dev, float *v_dev, double *partials_dev,
+                      float *norms_out_dev, long long t, float alpha, float clip, float b1, float b2, float eps, ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
