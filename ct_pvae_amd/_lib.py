@@ -207,6 +207,11 @@ SIGNATURES = {
     "ctpvae_update_plan_host": (_c_int, [_vp, _vp, _c_int, _vp]),
     "ctpvae_update_f32": (_c_int, [_vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_longlong, _c_float, _c_float, _c_float, _c_float,
                                    _c_float, _vp]),
+    "ctpvae_conv_wgrad_chunk_len": (_c_int, []),
+    "ctpvae_conv_wgrad_workspace_bytes": (ctypes.c_longlong, [_c_int] * 11),
+    "ctpvae_conv_fwd_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp]),
+    "ctpvae_conv_bwd_weight_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp, _vp]),
+    "ctpvae_conv_bwd_input_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp]),
 }
 
 _lib = None

@@ -921,6 +921,32 @@ int ctpvae_update_plan_host(const long long *lens_host, const void *const *param
 int ctpvae_update_f32(const void *plan_dev, int n_chunks, int T, const float *grad_dev, float *m_dev, float *v_dev, double *partials_dev,
                       float *norms_out_dev, long long t, float alpha, float clip, float b1, float b2, float eps, ctpvae_stream_t stream);
 
+/* ---- the convolution of a padded (non-transposed) ConvBlock with its periodic padding in front and its maxout behind, on the matrix
+ * cores with fp32 operands (csrc/conv.hip states every sum's one order, the tail rule, the chunk rule and how invalid taps enter);
+ * added without a new ABI version: nothing that existed changes.  All tensors fp32, contiguous NCHW: x_dev [N][Cin][H][W], w_dev
+ * [2C][Cin][k][k], b_dev [2C]; stride s; pads (wl, wr, hl, hr) >= 0; PH = H + hl + hr, PW = W + wl + wr, OH = (PH - k) / s + 1,
+ * OW = (PW - k) / s + 1; the padded input xp[n][ci][r][q] = x[n][ci][(r - hl) mod H][(q - wl) mod W] is never written to memory.
+ *   _fwd_f32: ONE launch.  y[n][c2][oh][ow] = one fmaf chain from b[c2] over ci, kh, kw ascending; out_dev [N][C][OH][OW] =
+ *     first ? y[c] : y[C + c] with first = y[c] >= y[C + c] (a tie takes the first half, a NaN the second), first_out_dev one byte
+ *     (0 or 1) per output element; y is not written.
+ *   _wgrad_chunk_len: the chunk length of the weight gradient's sum over m = (n * OH + oh) * OW + ow (host only).
+ *   _wgrad_workspace_bytes: 4 * ceil(N * OH * OW / chunk_len) * 2C * (Cin * k * k + 1), a function of the shapes alone (host only).
+ *   _bwd_weight_f32: TWO launches.  gw_out_dev [2C][Cin][k][k] and gb_out_dev [2C] of the cotangent g_dev [N][C][OH][OW] and
+ *     first_dev: per chunk one fmaf chain from +0 ascending in m, then the chunks' partials added in ascending order in fp32.
+ *   _bwd_input_f32: ONE launch.  gp_out_dev [N][Cin][PH][PW], the cotangent of the padded input: one fmaf chain from +0 over c2, kh,
+ *     kw ascending; ctpvae_periodic_pad_bwd_f32(gp, N * Cin, H, W, wl, wr, hl, hr, gx) folds it into the input's gradient.
+ * 1 <= k <= 8, 1 <= s <= k, k <= PH, k <= PW, every extent >= 1, every element count (the tensors, gp, the workspace) <= 2^31 - 1;
+ * every check is made before any launch. */
+int ctpvae_conv_wgrad_chunk_len(void);
+long long ctpvae_conv_wgrad_workspace_bytes(int N, int Cin, int H, int W, int C, int k, int s, int wl, int wr, int hl, int hr);
+int ctpvae_conv_fwd_f32(const float *x_dev, const float *w_dev, const float *b_dev, int N, int Cin, int H, int W, int C, int k, int s, int wl,
+                        int wr, int hl, int hr, float *out_dev, unsigned char *first_out_dev, ctpvae_stream_t stream);
+int ctpvae_conv_bwd_weight_f32(const float *x_dev, const float *g_dev, const unsigned char *first_dev, int N, int Cin, int H, int W, int C,
+                               int k, int s, int wl, int wr, int hl, int hr, void *workspace_dev, float *gw_out_dev, float *gb_out_dev,
+                               ctpvae_stream_t stream);
+int ctpvae_conv_bwd_input_f32(const float *g_dev, const unsigned char *first_dev, const float *w_dev, int N, int Cin, int H, int W, int C,
+                              int k, int s, int wl, int wr, int hl, int hr, float *gp_out_dev, ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
