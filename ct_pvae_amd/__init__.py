@@ -18,6 +18,7 @@ from .latents import latent_draws, normal_latents  # noqa: F401
 from .marginals import PixelMarginals, bin_samples  # noqa: F401
 from .convblock import dropout, dropout_mask, dropout_pad, maxout, periodic_pad  # noqa: F401
 from .conv import periodic_conv_maxout  # noqa: F401
+from .conv_transpose import conv_transpose_maxout  # noqa: F401
 from .merit import image_merits  # noqa: F401
 from .update import FusedUpdate, adam_alpha  # noqa: F401
 

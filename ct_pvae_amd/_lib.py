@@ -212,6 +212,10 @@ SIGNATURES = {
     "ctpvae_conv_fwd_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp]),
     "ctpvae_conv_bwd_weight_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp, _vp, _vp]),
     "ctpvae_conv_bwd_input_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 11 + [_vp, _vp]),
+    "ctpvae_convt_wgrad_workspace_bytes": (ctypes.c_longlong, [_c_int] * 9),
+    "ctpvae_convt_fwd_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 9 + [_vp, _vp, _vp]),
+    "ctpvae_convt_bwd_weight_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 9 + [_vp, _vp, _vp, _vp]),
+    "ctpvae_convt_bwd_input_f32": (_c_int, [_vp, _vp, _vp] + [_c_int] * 9 + [_vp, _vp]),
 }
 
 _lib = None

@@ -48,15 +48,9 @@
 #include <climits>
 
 #include "common.h"
+#include "conv_tile.h"
 
 namespace ctpvae {
-
-constexpr int kConvThreads = 256;      // four waves
-constexpr int kConvChunk = 1024;       // the chunk rule of the weight gradient
-constexpr int kConvMaxK = 8;
-constexpr int kConvDepth = 4;          // steps of the k loop whose loads are issued before their MFMAs; no effect on any result
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct ConvGeom {
     int N, Cin, H, W, C, k, s;
@@ -64,8 +58,6 @@ struct ConvGeom {
     int sr0, sq0;                      // source row / column of padded row / column 0: (-hl) mod H, (-wl) mod W
     int sH, sW;                        // s mod H, s mod W
 };
-
-__device__ __forceinline__ int tile_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 // out pixels on the columns, channel pairs on the rows; k runs over (ci, kh, kw)
 __global__ __launch_bounds__(kConvThreads) void conv_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,

@@ -36,6 +36,7 @@ import torch.nn as nn
 
 from . import convblock, dataset_io, phantoms, sharding
 from .conv import periodic_conv_maxout
+from .conv_transpose import conv_transpose_maxout
 from .convblock import dropout, dropout_pad, maxout, periodic_pad
 from .create_masks import create_all_masks
 from .fbp import iradon_all
@@ -144,12 +145,16 @@ class ConvBlock(nn.Module):
     convolution, which has no pad, either way.  The mask is a function of (seed, draw, layer, global object, element): no generator
     state, nothing stored for the backward.  fused_conv: a non-transposed block is ONE launch, conv.periodic_conv_maxout on ab's own
     weight and bias (csrc/conv.hip: padding, convolution and maxout with every sum in one stated order), after convblock.dropout
-    where the block drops -- the bits of dropout_pad followed by that convolution; a transposed block is untouched by it."""
+    where the block drops -- the bits of dropout_pad followed by that convolution; a transposed block is untouched by it.
+    fused_convt: a transposed block is ONE launch, conv_transpose.conv_transpose_maxout on ab's own weight, bias, stride, padding and
+    output_padding (csrc/conv_transpose.hip: transposed convolution and maxout with every sum in one stated order), after
+    convblock.dropout where the block drops; a non-transposed block ignores it.  Parameters, names, initialisation and checkpoints
+    are the same with and without either flag."""
 
-    def __init__(self, cin, cout, k, stride, transpose, fused_blocks=False, dropout=None, layer=0, fused_conv=False):
+    def __init__(self, cin, cout, k, stride, transpose, fused_blocks=False, dropout=None, layer=0, fused_conv=False, fused_convt=False):
         super().__init__()
         self.k, self.stride, self.transpose, self.fused_blocks = k, stride, transpose, bool(fused_blocks)
-        self.fused_conv = bool(fused_conv)
+        self.fused_conv, self.fused_convt = bool(fused_conv), bool(fused_convt)
         self.dropout, self.layer = dropout, int(layer)
         # the two convolutions of the maxout are ONE convolution with 2 * cout output channels (half the launches);
         # each half is initialised as its own GlorotUniform layer
@@ -174,6 +179,9 @@ class ConvBlock(nn.Module):
         if self.transpose:
             if d is not None:
                 x = dropout(x.contiguous(), d.rate, **key)
+            if self.fused_convt:
+                return conv_transpose_maxout(x.contiguous(), self.ab.weight, self.ab.bias, self.ab.stride[0], self.ab.padding[0],
+                                             self.ab.output_padding[0])
         else:
             pads = []
             for n in (x.shape[-1], x.shape[-2]):   # last axis first, as torch.nn.functional.pad orders them
@@ -197,7 +205,7 @@ class EncodeNet(nn.Module):
     """create_encode_net, ctvae/models.py:23-108: returns the list of skips (the first one is the repeated input)."""
 
     def __init__(self, cin, feature_maps, fmm, kernel, stride, inter_layers, inter_kernel, fused_blocks=False, dropout=None, first_layer=0,
-                 fused_conv=False):
+                 fused_conv=False, fused_convt=False):
         super().__init__()
         self.fmm = fmm
         c = cin * fmm
@@ -206,10 +214,10 @@ class EncodeNet(nn.Module):
         self.dropout = dropout
         layer = iter(range(first_layer, 2 ** 24))            # the blocks' dropout layers: numbered in construction order
         for f in feature_maps:
-            layers = [ConvBlock(c, c, inter_kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer), fused_conv=fused_conv)
-                      for _ in range(inter_layers)]
+            layers = [ConvBlock(c, c, inter_kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer), fused_conv=fused_conv,
+                                fused_convt=fused_convt) for _ in range(inter_layers)]
             layers.append(ConvBlock(c, f * fmm, kernel, stride, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer),
-                                    fused_conv=fused_conv))
+                                    fused_conv=fused_conv, fused_convt=fused_convt))
             self.blocks.append(nn.Sequential(*layers))
             c = f * fmm
             self.channels.append(c)
@@ -228,7 +236,7 @@ class DecodeNet(nn.Module):
     """create_decode_net, ctvae/models.py:112-215 (the code concatenates every skip, including the input level)."""
 
     def __init__(self, enc_channels, fmm, out_channels, kernel, stride, inter_layers, inter_kernel, fused_blocks=False, dropout=None,
-                 first_layer=0, fused_conv=False):
+                 first_layer=0, fused_conv=False, fused_convt=False):
         super().__init__()
         lat = [c // fmm for c in enc_channels]     # channels of the sampled latents
         self.ups = nn.ModuleList()
@@ -237,13 +245,13 @@ class DecodeNet(nn.Module):
         c = lat[-1]
         for lvl in range(len(enc_channels) - 2, -1, -1):
             layers = [ConvBlock(c, enc_channels[lvl], kernel, stride, True, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer),
-                                fused_conv=fused_conv)]
+                                fused_conv=fused_conv, fused_convt=fused_convt)]
             layers += [ConvBlock(enc_channels[lvl], enc_channels[lvl], inter_kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout,
-                                 layer=next(layer), fused_conv=fused_conv) for _ in range(inter_layers)]
+                                 layer=next(layer), fused_conv=fused_conv, fused_convt=fused_convt) for _ in range(inter_layers)]
             self.ups.append(nn.Sequential(*layers))
             c = enc_channels[lvl] + lat[lvl]
         self.head = ConvBlock(c, 2 * out_channels, kernel, 1, False, fused_blocks=fused_blocks, dropout=dropout, layer=next(layer),
-                              fused_conv=fused_conv)
+                              fused_conv=fused_conv, fused_convt=fused_convt)
         self.num_layers = next(layer) - first_layer
 
     def forward(self, latents):
@@ -479,15 +487,17 @@ class PVAETrainer:
         fmm = 1 if a.deterministic else 2
         fused_blocks = bool(getattr(a, "fused_blocks", False))
         fused_conv = bool(getattr(a, "fused_conv", False))
+        fused_convt = bool(getattr(a, "fused_convt", False))
         # --dp: one DropoutKey per network (their batches differ: B objects in the encoder, ns * B sample-major in the decoder); the
         # blocks' layers run through the encoder, then the decoder.  With --dp 0 the networks are built exactly as without the flag.
         dp = float(getattr(a, "dropout_prob", 0.0) or 0.0)
         self.enc_drop = DropoutKey(dp, a.head_seed) if dp > 0 else None
         self.dec_drop = DropoutKey(dp, a.head_seed) if dp > 0 else None
         self.enc = EncodeNet(len(a.algorithms) + 1, fm, fmm, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks,
-                             dropout=self.enc_drop, fused_conv=fused_conv).to(device)
+                             dropout=self.enc_drop, fused_conv=fused_conv, fused_convt=fused_convt).to(device)
         self.dec = DecodeNet(self.enc.channels, fmm, 1, a.kernel_size, a.stride_encode, a.il, a.ik, fused_blocks=fused_blocks,
-                             dropout=self.dec_drop, first_layer=self.enc.num_layers, fused_conv=fused_conv).to(device)
+                             dropout=self.dec_drop, first_layer=self.enc.num_layers, fused_conv=fused_conv,
+                             fused_convt=fused_convt).to(device)
         if self.world > 1:   # identical initial weights on every rank
             for p in list(self.enc.parameters()) + list(self.dec.parameters()):
                 torch.distributed.broadcast(p.data, 0)
@@ -933,10 +943,20 @@ def get_args(argv=None):
                         "four backward launches on the matrix cores with fp32 operands (csrc/conv.hip) instead of MIOpen's convolutions "
                         "between the pad and the maxout: every sum in one stated order, so these blocks give the same bits from run to run "
                         "without torch's deterministic switch; the same parameters and checkpoints; the transposed blocks stay on torch "
-                        "(--reproducible still sets the switch for them); combinable with every other flag.  Measured at the c3 recipe "
+                        "(--reproducible still sets the switch for them) unless --fused_convt is given; combinable with every other flag.  Measured at the c3 recipe "
                         "(profiles/conv_timing.txt) on top of --fused_head --fused_latents --fused_blocks --fused_update: with "
                         "--reproducible 106.5 against 53.3 steps/s (the windows do not overlap); against the non-deterministic default "
                         "NOT faster, 106.5 against 245.0 steps/s")
+    p.add_argument("--fused_convt", action="store_true",
+                   help="every transposed (up-sampling) ConvBlock -- transposed convolution, maxout -- as one forward launch and at most "
+                        "three backward launches on the matrix cores with fp32 operands (csrc/conv_transpose.hip) instead of MIOpen's "
+                        "transposed convolution in front of the maxout: every sum in one stated order; the same parameters and "
+                        "checkpoints; independent of --fused_conv and combinable with every other flag.  With --fused_conv no "
+                        "convolution of the networks goes through MIOpen and two runs with equal seeds are bit-equal WITHOUT "
+                        "--reproducible.  Measured at the c3 recipe (profiles/conv_transpose_timing.txt) on top of --fused_head "
+                        "--fused_latents --fused_blocks --fused_update: --fused_conv --fused_convt 103.4 steps/s (103.3 .. 103.5), "
+                        "--reproducible --fused_conv 106.9 (106.7 .. 106.9), neither flag 286.2 (285.4 .. 286.5); the windows do not "
+                        "overlap: it is 3 %% SLOWER than --reproducible --fused_conv and NOT for runs that need no bit-equal step")
     p.add_argument("--fused_update", action="store_true",
                    help="the update stage -- NaN filter, per-tensor clip_by_norm (--norm), Adam (--lr, --ae) -- as two launches over the flat "
                         "gradient bucket (csrc/update.hip) instead of torch's chain and torch.optim.Adam: Keras's Adam, as the reference runs "

@@ -947,6 +947,32 @@ int ctpvae_conv_bwd_weight_f32(const float *x_dev, const float *g_dev, const uns
 int ctpvae_conv_bwd_input_f32(const float *g_dev, const unsigned char *first_dev, const float *w_dev, int N, int Cin, int H, int W, int C,
                               int k, int s, int wl, int wr, int hl, int hr, float *gp_out_dev, ctpvae_stream_t stream);
 
+/* ---- the transposed convolution of an up-sampling ConvBlock with its maxout behind, on the matrix cores with fp32 operands
+ * (csrc/conv_transpose.hip states every sum's one order, the phase taps, the tail rule, the two chunk rules and how invalid taps
+ * enter); added without a new ABI version: nothing that existed changes.  All tensors fp32, contiguous: x_dev [N][Cin][H][W], w_dev
+ * [Cin][2C][k][k] (nn.ConvTranspose2d's weight; the maxout's halves are [0, C) and [C, 2C) of axis 1), b_dev [2C]; stride s, padding
+ * pad, output padding opad; OH = (H - 1) * s - 2 * pad + k + opad, OW likewise.
+ *   _fwd_f32: ONE launch.  y[n][c2][oy][ox] = one fmaf chain from b[c2] over ci, the pixel's phase kh, its phase kw ascending (a phase
+ *     tap outside the image enters as +0, taps of other phases not at all); out_dev [N][C][OH][OW] = first ? y[c] : y[C + c] with
+ *     first = y[c] >= y[C + c] (a tie takes the first half, a NaN the second), first_out_dev one byte (0 or 1) per output element; y
+ *     is not written.
+ *   _wgrad_workspace_bytes: 4 * (ceil(N * H * W / chunk) * Cin * 2C * k * k + ceil(N * OH * OW / chunk) * 2C) with chunk =
+ *     ctpvae_conv_wgrad_chunk_len(), a function of the shapes alone (host only).
+ *   _bwd_weight_f32: TWO launches.  gw_out_dev [Cin][2C][k][k] and gb_out_dev [2C] of the cotangent g_dev [N][C][OH][OW] and
+ *     first_dev: gw per chunk of m = (n * H + iy) * W + ix one fmaf chain from +0 ascending in m, gb per chunk of
+ *     mo = (n * OH + oy) * OW + ox one chain of additions from +0 ascending in mo, then the partials added in ascending chunk order.
+ *   _bwd_input_f32: ONE launch.  gx_out_dev [N][Cin][H][W]: one fmaf chain from +0 over c2, kh, kw ascending.
+ * 1 <= k <= 8, 1 <= s <= k, 0 <= pad < k, 0 <= opad < s, OH >= 1, OW >= 1, every extent >= 1, every element count (the tensors, the
+ * workspace, the launches' workgroups) <= 2^31 - 1; every check is made before any launch. */
+long long ctpvae_convt_wgrad_workspace_bytes(int N, int Cin, int H, int W, int C, int k, int s, int pad, int opad);
+int ctpvae_convt_fwd_f32(const float *x_dev, const float *w_dev, const float *b_dev, int N, int Cin, int H, int W, int C, int k, int s, int pad,
+                         int opad, float *out_dev, unsigned char *first_out_dev, ctpvae_stream_t stream);
+int ctpvae_convt_bwd_weight_f32(const float *x_dev, const float *g_dev, const unsigned char *first_dev, int N, int Cin, int H, int W, int C,
+                                int k, int s, int pad, int opad, void *workspace_dev, float *gw_out_dev, float *gb_out_dev,
+                                ctpvae_stream_t stream);
+int ctpvae_convt_bwd_input_f32(const float *g_dev, const unsigned char *first_dev, const float *w_dev, int N, int Cin, int H, int W, int C,
+                               int k, int s, int pad, int opad, float *gx_out_dev, ctpvae_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
