@@ -1,0 +1,15 @@
+"""The one check of a float32 tensor argument that every fused operator makes before it looks at a device."""
+import torch
+
+
+def check_float32(what, name, t, dim, layout, shape_ok=None):
+    """Refuse, in this order: a non-tensor and a dtype other than float32 (TypeError); a rank other than `dim`, an empty tensor or a
+    shape that `shape_ok(t.shape)` turns down, as "`what`: `name` must be `layout`"; a non-contiguous tensor (ValueError)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: {name} must be a torch tensor (got {type(t).__name__})")
+    if t.dtype is not torch.float32:
+        raise TypeError(f"{what}: {name} must be float32 (got {t.dtype})")
+    if t.dim() != dim or t.numel() == 0 or (shape_ok is not None and not shape_ok(t.shape)):
+        raise ValueError(f"{what}: {name} must be {layout} (got {tuple(t.shape)})")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous (got strides {tuple(t.stride())})")

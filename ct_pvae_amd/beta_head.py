@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
@@ -36,14 +37,7 @@ def beta_head_words(n, pix, *, seed, draw, first_object=0, gamma, attempt):
 
 
 def _check_input(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"beta_head: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"beta_head: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.shape[1] != 1 or t.numel() == 0:
-        raise ValueError(f"beta_head: {name} must be [n][1][X][Y], the decoder's layout (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"beta_head: {name} must be contiguous (got strides {tuple(t.stride())})")
+    check_float32("beta_head", name, t, 4, "[n][1][X][Y], the decoder's layout", lambda shape: shape[1] == 1)
 
 
 class _BetaHead(torch.autograd.Function):

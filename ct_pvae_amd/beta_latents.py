@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
@@ -49,14 +50,7 @@ def beta_latent_words(n, length, *, seed, draw, level, s, gamma, attempt, first_
 
 
 def _check_input(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"beta_latents: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"beta_latents: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.numel() == 0:
-        raise ValueError(f"beta_latents: {name} must be [B][channels][H][W], the encoder's layout (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"beta_latents: {name} must be contiguous (got strides {tuple(t.stride())})")
+    check_float32("beta_latents", name, t, 4, "[B][channels][H][W], the encoder's layout")
 
 
 class _BetaLatents(torch.autograd.Function):

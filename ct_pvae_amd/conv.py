@@ -10,31 +10,21 @@ The padded input and the convolution's 2C-channel result are never written to me
 output element.  There is no CPU path."""
 import torch
 
+from . import _conv_common as common
 from . import _lib, forward_functions
 from .forward_functions import _stream_ptr
 
 __all__ = ["periodic_conv_maxout"]
 
 
-def _check_tensor(name, t, dim):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"periodic_conv_maxout: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"periodic_conv_maxout: {name} must be float32 (got {t.dtype})")
-    if t.dim() != dim or t.numel() == 0:
-        raise ValueError(f"periodic_conv_maxout: {name} must be a non-empty tensor of {dim} axes (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"periodic_conv_maxout: {name} must be contiguous (got strides {tuple(t.stride())})")
+WHAT, PREFIX = "periodic_conv_maxout", "conv"     # the operator's name in messages, the stem of its C symbols
 
 
 def _geometry(x, weight, bias, stride, pads):
     """The eleven integers of the C ABI, (N, Cin, H, W, C, k, s, wl, wr, hl, hr), and the output's (OH, OW); every check that needs no
     device, before any launch."""
-    _check_tensor("x", x, 4)
-    _check_tensor("weight", weight, 4)
-    _check_tensor("bias", bias, 1)
-    if isinstance(stride, bool) or not isinstance(stride, int):
-        raise TypeError(f"periodic_conv_maxout: stride must be a Python int (got {type(stride).__name__})")
+    common.check_tensors(WHAT, x, weight, bias)
+    common.check_ints(WHAT, stride=stride)
     pads = tuple(int(p) for p in pads)
     if len(pads) != 4 or min(pads) < 0:
         raise ValueError(f"periodic_conv_maxout: pads must be four non-negative integers (wl, wr, hl, hr) (got {pads})")
@@ -44,10 +34,7 @@ def _geometry(x, weight, bias, stride, pads):
         raise ValueError(f"periodic_conv_maxout: weight must be [2C][Cin = {Cin}][k][k], the two convolutions' halves (got {tuple(weight.shape)})")
     if tuple(bias.shape) != (C2,):
         raise ValueError(f"periodic_conv_maxout: bias must be [2C = {C2}] (got {tuple(bias.shape)})")
-    if not 1 <= k <= 8:
-        raise ValueError(f"periodic_conv_maxout: the kernel size must be in 1 .. 8 (got {k})")
-    if not 1 <= stride <= k:
-        raise ValueError(f"periodic_conv_maxout: the stride must be in 1 .. k = {k} (got {stride})")
+    common.check_kernel_and_stride(WHAT, k, stride)
     wl, wr, hl, hr = pads
     PH, PW = H + hl + hr, W + wl + wr
     if PH < k or PW < k:
@@ -59,20 +46,10 @@ def _geometry(x, weight, bias, stride, pads):
     return (N, Cin, H, W, C2 // 2, k, stride, wl, wr, hl, hr), (OH, OW)
 
 
-def _forward(x, weight, bias, geom, hw):
-    N, C = geom[0], geom[4]
-    out = forward_functions._new_output((N, C) + hw, torch.float32, x.device)
-    first = torch.empty((N, C) + hw, dtype=torch.uint8, device=x.device)     # (saved state, every byte written by the launch)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().ctpvae_conv_fwd_f32(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), *geom, out.data_ptr(), first.data_ptr(),
-                                                   _stream_ptr()), "conv_fwd")
-    return out, first
-
-
 class _PeriodicConvMaxout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, geom, hw):
-        out, first = _forward(x, weight, bias, geom, hw)
+        out, first = common.forward(PREFIX, x, weight, bias, geom, hw)
         ctx.save_for_backward(x, weight, first)       # never the 2C-channel result or a padded copy
         ctx.geom = geom
         ctx.set_materialize_grads(False)
@@ -85,19 +62,14 @@ class _PeriodicConvMaxout(torch.autograd.Function):
             return None, None, None, None, None
         x, weight, first = ctx.saved_tensors
         geom = ctx.geom
-        N, Cin, H, W, C, k, s, wl, wr, hl, hr = geom
+        N, Cin, H, W, _, _, _, wl, wr, hl, hr = geom
         g = g.to(torch.float32).contiguous()
-        lib = _lib.load()
         gx = gw = gb = None
-        with torch.cuda.device(g.device):
-            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                ws = torch.empty(_lib.check(lib.ctpvae_conv_wgrad_workspace_bytes(*geom), "conv_wgrad_workspace_bytes") // 4,
-                                 dtype=torch.float32, device=g.device)
-                gw = forward_functions._new_output(tuple(weight.shape), torch.float32, g.device)
-                gb = forward_functions._new_output((2 * C,), torch.float32, g.device)
-                _lib.check(lib.ctpvae_conv_bwd_weight_f32(x.data_ptr(), g.data_ptr(), first.data_ptr(), *geom, ws.data_ptr(), gw.data_ptr(),
-                                                          gb.data_ptr(), _stream_ptr()), "conv_bwd_weight")
-            if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw, gb = common.weight_grad(PREFIX, x, g, first, weight, geom)
+        if ctx.needs_input_grad[0]:
+            lib = _lib.load()
+            with torch.cuda.device(g.device):
                 gp = forward_functions._new_output((N, Cin, H + hl + hr, W + wl + wr), torch.float32, g.device)
                 _lib.check(lib.ctpvae_conv_bwd_input_f32(g.data_ptr(), first.data_ptr(), weight.data_ptr(), *geom, gp.data_ptr(),
                                                          _stream_ptr()), "conv_bwd_input")
@@ -107,20 +79,12 @@ class _PeriodicConvMaxout(torch.autograd.Function):
         return (gx, gw if ctx.needs_input_grad[1] else None, gb if ctx.needs_input_grad[2] else None, None, None)
 
 
-def _require_cuda(x, weight, bias):
-    for name, t in (("x", x), ("weight", weight), ("bias", bias)):
-        if t.device.type != "cuda":
-            raise _lib.RadonLibraryError(f"periodic_conv_maxout: {name} must be a CUDA tensor; there is no CPU path")
-        if t.device != x.device:
-            raise ValueError(f"periodic_conv_maxout: {name} is on {t.device}, x on {x.device}")
-
-
 def _conv_maxout_with_first(x, weight, bias, stride, pads):
     """(out, first) of the forward launch, detached: first [N][C][OH][OW], uint8, 1 where the first channel half was taken (a tie
     takes it, a NaN on either side does not).  For tests and tools that read the selection; arguments as periodic_conv_maxout's."""
     geom, hw = _geometry(x, weight, bias, stride, pads)
-    _require_cuda(x, weight, bias)
-    return _forward(x.detach(), weight.detach(), bias.detach(), geom, hw)
+    common.require_cuda(WHAT, x, weight, bias)
+    return common.forward(PREFIX, x.detach(), weight.detach(), bias.detach(), geom, hw)
 
 
 def periodic_conv_maxout(x, weight, bias, stride, pads):
@@ -133,5 +97,5 @@ def periodic_conv_maxout(x, weight, bias, stride, pads):
     taken by selection; the weight gradient's sum over the N * OH * OW output pixels is cut into chunks of 1024 by the shapes alone, so
     every gradient has the same bits on every run (csrc/conv.hip)."""
     geom, hw = _geometry(x, weight, bias, stride, pads)
-    _require_cuda(x, weight, bias)
+    common.require_cuda(WHAT, x, weight, bias)
     return _PeriodicConvMaxout.apply(x, weight, bias, geom, hw)

@@ -24,21 +24,14 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
 __all__ = ["periodic_pad", "maxout", "dropout", "dropout_pad", "dropout_mask"]
 
 
-def _check_input(what, name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{what}: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"{what}: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.numel() == 0:
-        raise ValueError(f"{what}: {name} must be a non-empty [N][C][H][W] tensor (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: {name} must be contiguous (got strides {tuple(t.stride())})")
+NCHW = "a non-empty [N][C][H][W] tensor"
 
 
 class _FusedPeriodicPad(torch.autograd.Function):
@@ -202,7 +195,7 @@ def dropout(x, rate, *, seed, draw, layer, first_object=0):
     depends on (seed, draw, layer, first_object + n, element) alone: pass the step index as `draw`, the block's number as `layer` and
     the offset of x's first object in the global batch as `first_object`, and a batch cut over calls or ranks drops what the whole
     batch drops.  Differentiable once in x: gx = where(keep, scale * g, +0), the mask drawn again -- the forward saves no tensor."""
-    _check_input("dropout", "x", x)
+    check_float32("dropout", "x", x, 4, NCHW)
     key_rate = _rate_args("dropout", rate)
     if x.numel() >= 2 ** 31:
         raise ValueError(f"dropout: at most 2^31 - 1 elements per call (got {tuple(x.shape)})")
@@ -217,7 +210,7 @@ def dropout_pad(x, pads, rate, *, seed, draw, layer, first_object=0):
     to the source element, so every wrapped copy of an element shares its fate; the backward is periodic_pad's gather with its order
     of addition, then where(keep, scale * sum, +0) at the source element, the mask drawn again -- the forward saves no tensor.
     x, rate and the keyword arguments as dropout's, pads = (wl, wr, hl, hr) as periodic_pad's."""
-    _check_input("dropout_pad", "x", x)
+    check_float32("dropout_pad", "x", x, 4, NCHW)
     pads = _pads_args("dropout_pad", x, pads)
     key_rate = _rate_args("dropout_pad", rate)
     seed, draw, layer, first_object = _key_args("dropout_pad", seed, draw, layer, first_object, x.shape[0], x.numel() // x.shape[0])
@@ -233,7 +226,7 @@ def periodic_pad(x, pads):
     deterministic gather with a fixed order of addition: per padded row the cotangents of a source column's copies are added in
     ascending q, then the rows of a source row in ascending r, each sum starting from its first term -- the same bits from run to
     run; with at most two copies per axis (every pad of the trainer's recipes) the value of trainer._PeriodicPad's index_add_ chain."""
-    _check_input("periodic_pad", "x", x)
+    check_float32("periodic_pad", "x", x, 4, NCHW)
     pads = _pads_args("periodic_pad", x, pads)
     if x.device.type != "cuda":
         raise _lib.RadonLibraryError("periodic_pad: x must be a CUDA tensor; there is no CPU path")
@@ -246,7 +239,7 @@ def maxout(y):
     MaximumGrad), a NaN in either half makes the comparison false and takes the second half, -0.0 >= +0.0 is true.  Differentiable
     once in y: the cotangent goes to the half that was taken and +0 to the other, by selection (an infinite cotangent gives inf and 0,
     where g * first gives inf and NaN).  The backward keeps one byte per output element, never a copy of y."""
-    _check_input("maxout", "y", y)
+    check_float32("maxout", "y", y, 4, NCHW)
     if y.shape[1] % 2 != 0:
         raise ValueError(f"maxout: y needs an even channel count, the two convolutions' halves (got {tuple(y.shape)})")
     if y.numel() >= 2 ** 31:

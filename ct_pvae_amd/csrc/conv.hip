@@ -8,15 +8,9 @@
 // K = Cin * k * k.  xp[n][ci][r][q] = x[n][ci][(r - hl) mod H][(q - wl) mod W] (the mathematical modulo; a pad may exceed the extent)
 // is never written to memory: every kernel reads x at wrapped addresses.
 //
-// The matrix instruction.  D = A * B + C with A [32][2], B [2][32], C/D [32][32]: lane l holds A[l & 31][l >> 5] and B[l >> 5][l & 31];
-// register g of lane l holds D[(g & 3) + 8 * (g >> 2) + 4 * (l >> 5)][l & 31].  Per element it is the chain
-// fmaf(a1, b1, fmaf(a0, b0, c)) -- k ascending, one rounding per product -- so a loop of them over ascending k is one fmaf chain.
-// (tests/test_gpu_conv.py checks the lane maps with small asymmetric integers and the chain by bits against the twin: on the MI355X
-// the instruction delivers exactly these bits, so no kernel here has an explicit-fmaf VALU path.)
-// Channels lie on the ROWS (A = weights or cotangents), pixels or taps on the COLUMNS (B), so a register's 32 lanes store 32
-// consecutive floats.  A wave computes TWO tiles that share B: rows c0 .. c0 + 31 of the first channel half and the SAME channels of
-// the second half, so the maxout's two operands meet in one register slot of one lane.
-// An operand outside its range (a row past C or Cin, a column past the pixels, a k past the sum's length) is fed as +0.
+// The matrix instruction: conv_tile.h states its lane maps, its k-ascending fmaf chain, which operand lies on the rows and which on
+// the columns, the wave's pair of tiles and the rule that an operand outside its range is fed as +0; the helpers on the tile that
+// this file shares with conv_transpose.hip are there too.
 //
 // Forward, one launch, a wave per (object, 32 channel pairs, 32 output pixels), four waves (128 pixels) per workgroup:
 //   y[n][c2][oh][ow]: acc = b[c2]; for ci ASCENDING, kh ASCENDING, kw ASCENDING: acc = fmaf(xp[n][ci][oh*s + kh][ow*s + kw], w[c2][ci][kh][kw], acc)
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_fwd_kernel(const float *__r
                                                                 const float *__restrict__ b, ConvGeom gm, int ctiles, int pgroups,
                                                                 float *__restrict__ out, unsigned char *__restrict__ first_out)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     int blk = blockIdx.x;
     const int pg = blk % pgroups;
     blk /= pgroups;
@@ -115,17 +109,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_fwd_kernel(const float *__r
             }
     }
     if (!pvalid) return;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int cr = ct * 32 + tile_row(g, half);
-        if (cr < gm.C) {
-            const float a = accA[g], bb = accB[g];
-            const bool first = a >= bb;
-            const size_t o = ((size_t)n * gm.C + cr) * gm.P + p;
-            out[o] = first ? a : bb;
-            first_out[o] = first ? 1 : 0;
-        }
-    }
+    tile_store_maxout(accA, accB, ct, half, n, gm.C, gm.P, p, out, first_out);
 }
 
 // taps (and the bias's constant 1) on the columns, channel pairs on the rows; k runs over the m of one chunk
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_wgrad_kernel(const float *_
                                                                   const unsigned char *__restrict__ first_in, ConvGeom gm, int ctiles,
                                                                   int kgroups, int M, float *__restrict__ part)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     int blk = blockIdx.x;
     const int kg = blk % kgroups;
     blk /= kgroups;
@@ -144,7 +128,8 @@ __global__ __launch_bounds__(kConvThreads) void conv_wgrad_kernel(const float *_
     const int kk2 = gm.k * gm.k;
     const int ci = kvalid ? kidx / kk2 : 0, rem = kvalid ? kidx - ci * kk2 : 0, kh = rem / gm.k, kw = rem - kh * gm.k;
     const int rrbase = (kh + gm.sr0) % gm.H, cqbase = (kw + gm.sq0) % gm.W;
-    const int m_begin = chunk * kConvChunk, m_end = M - m_begin < kConvChunk ? M : m_begin + kConvChunk;
+    int m_begin, m_end;
+    chunk_range(chunk, M, m_begin, m_end);
     int m = m_begin + half;
     int n = m / gm.P, pix = m - n * gm.P, oh = pix / gm.OW, ow = pix - oh * gm.OW;
     int rr = (oh * gm.s + rrbase) % gm.H, cq = (ow * gm.s + cqbase) % gm.W;
@@ -161,8 +146,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_wgrad_kernel(const float *_
     const bool cvalid = c < gm.C;
     const int HW = gm.H * gm.W;
     f32x16 accA, accB;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accA[r] = 0.0f, accB[r] = 0.0f;
+    tile_zero(accA), tile_zero(accB);
     for (int mb = m_begin; mb < m_end; mb += 2 * kConvDepth) {   // mb is wave-uniform
         float gv[kConvDepth], xv[kConvDepth];
         unsigned char fb[kConvDepth];
@@ -181,11 +165,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_wgrad_kernel(const float *_
         m += 2 * kConvDepth;
 #pragma unroll
         for (int u = 0; u < kConvDepth; ++u)
-            if (mb + 2 * u < m_end) {
-                const bool first = fb[u] != 0;
-                accA = __builtin_amdgcn_mfma_f32_32x32x2f32(first ? gv[u] : 0.0f, xv[u], accA, 0, 0, 0);
-                accB = __builtin_amdgcn_mfma_f32_32x32x2f32(first ? 0.0f : gv[u], xv[u], accB, 0, 0, 0);
-            }
+            if (mb + 2 * u < m_end) tile_mfma_selected(accA, accB, fb[u] != 0, gv[u], xv[u]);
     }
     if (kidx > gm.K) return;
     const size_t row = (size_t)gm.K + 1, base = (size_t)chunk * 2 * gm.C;
@@ -206,8 +186,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_wgrad_finish_kernel(const f
     const unsigned total = (unsigned)C2 * (unsigned)(K + 1);
     const unsigned e = blockIdx.x * kConvThreads + threadIdx.x;
     if (e >= total) return;
-    float acc = part[e];
-    for (int jc = 1; jc < chunks; ++jc) acc = acc + part[(size_t)jc * total + e];
+    const float acc = chunk_sum(part, chunks, total, e);
     const unsigned c2 = e / (unsigned)(K + 1), kidx = e - c2 * (unsigned)(K + 1);
     if (kidx < (unsigned)K) gw[(size_t)c2 * K + kidx] = acc;
     else gb[c2] = acc;
@@ -219,7 +198,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_dgrad_kernel(const float *_
                                                                   float *__restrict__ gp)
 {
     __shared__ int tab[4][2][kConvMaxK][32];            // per wave: [0][kh][j] = oh * OW or -1, [1][kw][j] = ow or -1
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     int blk = blockIdx.x;
     const int pg = blk % pgroups;
     blk /= pgroups;
@@ -248,8 +227,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_dgrad_kernel(const float *_
     const int ci = cit * 32 + j;                        // this lane's ROW of the A operand
     const bool civalid = ci < gm.Cin;
     f32x16 acc;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
+    tile_zero(acc);
     for (int kb = 0; kb < K2; kb += 2 * kConvDepth) {         // kb is wave-uniform
         float gv[kConvDepth], wv_[kConvDepth];
         unsigned char take[kConvDepth];                        // 1: the cotangent goes to this c2's half
@@ -283,10 +261,7 @@ __global__ __launch_bounds__(kConvThreads) void conv_dgrad_kernel(const float *_
 
 static int conv_check(const char *what, int N, int Cin, int H, int W, int C, int k, int s, int wl, int wr, int hl, int hr, ConvGeom *gm)
 {
-    CTPVAE_REQUIRE(N >= 1 && Cin >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: extents must be at least 1 (N=%d Cin=%d H=%d W=%d C=%d)", what, N,
-                   Cin, H, W, C);
-    CTPVAE_REQUIRE(k >= 1 && k <= kConvMaxK, "%s: the kernel size must be in 1 .. %d (got %d)", what, kConvMaxK, k);
-    CTPVAE_REQUIRE(s >= 1 && s <= k, "%s: the stride must be in 1 .. k (got s=%d k=%d)", what, s, k);
+    if (int rc = conv_check_common(what, N, Cin, H, W, C, k, s)) return rc;
     CTPVAE_REQUIRE(wl >= 0 && wr >= 0 && hl >= 0 && hr >= 0, "%s: pads must not be negative (wl=%d wr=%d hl=%d hr=%d)", what, wl, wr, hl, hr);
     const long long PH = (long long)H + hl + hr, PW = (long long)W + wl + wr;
     CTPVAE_REQUIRE(PH >= k && PW >= k, "%s: the padded image (%lld x %lld) must hold one window of %d x %d", what, PH, PW, k, k);
@@ -303,12 +278,10 @@ static int conv_check(const char *what, int N, int Cin, int H, int W, int C, int
     return CTPVAE_OK;
 }
 
-static long long conv_tiles(long long n, int per) { return (n + per - 1) / per; }
-
 // chunks of the weight gradient and the floats of its workspace; -1 when the workspace's element count does not fit 31 bits
 static long long conv_wgrad_floats(const ConvGeom &gm, int *chunks)
 {
-    const long long M = (long long)gm.N * gm.P, ch = conv_tiles(M, kConvChunk), fl = ch * 2 * gm.C * ((long long)gm.K + 1);
+    const long long M = (long long)gm.N * gm.P, ch = ceil_div(M, kConvChunk), fl = ch * 2 * gm.C * ((long long)gm.K + 1);
     *chunks = (int)ch;
     return fl <= INT_MAX ? fl : -1;
 }
@@ -337,8 +310,8 @@ int ctpvae_conv_fwd_f32(const float *x_dev, const float *w_dev, const float *b_d
     CTPVAE_REQUIRE(x_dev && w_dev && b_dev && out_dev && first_out_dev, "conv_fwd: null pointer");
     ConvGeom gm;
     if (int rc = conv_check("conv_fwd", N, Cin, H, W, C, k, s, wl, wr, hl, hr, &gm)) return rc;
-    const long long ctiles = conv_tiles(C, 32), pgroups = conv_tiles(gm.P, 128), blocks = (long long)N * ctiles * pgroups;
-    CTPVAE_REQUIRE(blocks <= INT_MAX, "conv_fwd: %lld workgroups do not fit 31 bits", blocks);
+    const long long ctiles = ceil_div(C, 32), pgroups = ceil_div(gm.P, 128), blocks = (long long)N * ctiles * pgroups;
+    if (int rc = conv_check_blocks("conv_fwd", blocks)) return rc;
     hipLaunchKernelGGL(conv_fwd_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, x_dev, w_dev, b_dev, gm,
                        (int)ctiles, (int)pgroups, out_dev, first_out_dev);
     CTPVAE_LAUNCH_CHECK("conv_fwd_kernel");
@@ -355,8 +328,8 @@ int ctpvae_conv_bwd_weight_f32(const float *x_dev, const float *g_dev, const uns
     int chunks;
     CTPVAE_REQUIRE(conv_wgrad_floats(gm, &chunks) >= 0, "conv_bwd_weight: chunks * 2C * (K + 1) must fit 31 bits (chunks=%d C=%d K=%d)",
                    chunks, C, gm.K);
-    const long long ctiles = conv_tiles(C, 32), kgroups = conv_tiles((long long)gm.K + 1, 128), blocks = chunks * ctiles * kgroups;
-    CTPVAE_REQUIRE(blocks <= INT_MAX, "conv_bwd_weight: %lld workgroups do not fit 31 bits", blocks);
+    const long long ctiles = ceil_div(C, 32), kgroups = ceil_div((long long)gm.K + 1, 128), blocks = chunks * ctiles * kgroups;
+    if (int rc = conv_check_blocks("conv_bwd_weight", blocks)) return rc;
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, x_dev, g_dev, first_dev, gm,
                        (int)ctiles, (int)kgroups, N * gm.P, (float *)workspace_dev);
     CTPVAE_LAUNCH_CHECK("conv_wgrad_kernel");
@@ -373,8 +346,8 @@ int ctpvae_conv_bwd_input_f32(const float *g_dev, const unsigned char *first_dev
     CTPVAE_REQUIRE(g_dev && first_dev && w_dev && gp_out_dev, "conv_bwd_input: null pointer");
     ConvGeom gm;
     if (int rc = conv_check("conv_bwd_input", N, Cin, H, W, C, k, s, wl, wr, hl, hr, &gm)) return rc;
-    const long long citiles = conv_tiles(Cin, 32), pgroups = conv_tiles((long long)gm.PH * gm.PW, 128), blocks = (long long)N * citiles * pgroups;
-    CTPVAE_REQUIRE(blocks <= INT_MAX, "conv_bwd_input: %lld workgroups do not fit 31 bits", blocks);
+    const long long citiles = ceil_div(Cin, 32), pgroups = ceil_div((long long)gm.PH * gm.PW, 128), blocks = (long long)N * citiles * pgroups;
+    if (int rc = conv_check_blocks("conv_bwd_input", blocks)) return rc;
     hipLaunchKernelGGL(conv_dgrad_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, g_dev, first_dev, w_dev, gm,
                        (int)citiles, (int)pgroups, gp_out_dev);
     CTPVAE_LAUNCH_CHECK("conv_dgrad_kernel");

@@ -1,8 +1,9 @@
 // conv_transpose.hip -- the transposed convolution of an up-sampling ConvBlock (ctvae/models.py:267-342, Conv2DTranspose; ct_pvae_amd/
 // trainer.py ConvBlock with transpose=True) with its maxout behind, as ONE forward launch and at most three backward launches, on the
-// matrix cores with fp32 operands (v_mfma_f32_32x32x2_f32; conv.hip's header states the instruction's lane maps and its chain,
-// conv_tile.h the shared constants).  Every sum has ONE stated order; no atomics; nothing depends on the device, its CU count, a knob or
-// launch-time state; tests/np_twin_conv_transpose.py restates this header and the kernels are held to it BY BITS.
+// matrix cores with fp32 operands (v_mfma_f32_32x32x2_f32; conv_tile.h states the instruction's lane maps and its chain and holds
+// the constants and the helpers on the tile that this file shares with conv.hip).  Every sum has ONE stated order; no atomics;
+// nothing depends on the device, its CU count, a knob or launch-time state; tests/np_twin_conv_transpose.py restates this header and
+// the kernels are held to it BY BITS.
 //
 // Operands, all contiguous fp32: x [N][Cin][H][W], w [Cin][2C][k][k] (nn.ConvTranspose2d's weight, read where the module keeps it; the
 // maxout's halves are the ranges [0, C) and [C, 2C) of axis 1), b [2C], stride s, padding pad, output padding opad.
@@ -69,25 +70,12 @@ struct ConvtGeom {
 // the first output index of phase ph along an axis: the smallest o >= 0 with (o + pad) mod s == ph
 __device__ __forceinline__ int convt_phase_first(int ph, int pad, int s) { return ((ph - pad) % s + s) % s; }
 
-// p[i] where ok, +0 elsewhere, with no branch: the load is always issued (from element 0 where !ok, which every operand has) and its
-// BITS are masked, which is a selection (a NaN or an infinity that is not wanted leaves no trace).  So a group's loads stay in
-// flight together; written as a select of the loaded value the compiler puts each load behind a branch of its own and waits there.
-__device__ __forceinline__ float load_or_zero(const float *__restrict__ p, bool ok, size_t i)
-{
-    return __uint_as_float(__float_as_uint(p[ok ? i : 0]) & (ok ? 0xffffffffu : 0u));
-}
-
-__device__ __forceinline__ unsigned char load_or_zero(const unsigned char *__restrict__ p, bool ok, size_t i)
-{
-    return (unsigned char)(p[ok ? i : 0] & (ok ? 0xffu : 0u));
-}
-
 // output pixels of one phase on the columns, channel pairs on the rows; k runs over (ci, phase kh, phase kw)
 __global__ __launch_bounds__(kConvThreads) void convt_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                                  const float *__restrict__ b, ConvtGeom gm, int ctiles, int pgroups,
                                                                  float *__restrict__ out, unsigned char *__restrict__ first_out)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     int blk = blockIdx.x;
     const int pg = blk % pgroups;
     blk /= pgroups;
@@ -145,17 +133,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_fwd_kernel(const float *__
     }
     if (!pvalid) return;
     const int oy = oy0 + gm.s * r, ox = ox0 + gm.s * cc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int cr = ct * 32 + tile_row(g, half);
-        if (cr < gm.C) {
-            const float va = accA[g], vb = accB[g];
-            const bool first = va >= vb;
-            const size_t o = ((size_t)n * gm.C + cr) * gm.P + oy * gm.OW + ox;
-            out[o] = first ? va : vb;
-            first_out[o] = first ? 1 : 0;
-        }
-    }
+    tile_store_maxout(accA, accB, ct, half, n, gm.C, gm.P, oy * gm.OW + ox, out, first_out);
 }
 
 // input pixels on the columns, input channels on the rows; k runs over (c2, kh, kw).  ONE tile per wave (there is no pair here).
@@ -163,7 +141,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_dgrad_kernel(const float *
                                                                    const float *__restrict__ w, ConvtGeom gm, int citiles, int pgroups,
                                                                    float *__restrict__ gx)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     int blk = blockIdx.x;
     const int pg = blk % pgroups;
     blk /= pgroups;
@@ -186,8 +164,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_dgrad_kernel(const float *
     const bool civalid = ci < gm.Cin;
     const float *wr = w + (size_t)(civalid ? ci : 0) * K2;      // w[ci][c2][kh][kw]: the chain's index is the offset
     f32x16 acc;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
+    tile_zero(acc);
     int left = K2 - half;                               // steps of the chain from this lane's next one on (it may fall below 0)
     auto fetch = [&](float (&gq)[kConvtDepth], float (&wq)[kConvtDepth], unsigned char (&tq)[kConvtDepth]) {
 #pragma unroll
@@ -234,7 +211,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_wgrad_kernel(const float *
                                                                    int citiles, int wwaves, int wblocks, int bwaves, int M, int Mo,
                                                                    float *__restrict__ part, float *__restrict__ partb)
 {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, half = lane >> 5;
+    const auto [wv, j, half] = tile_lane();
     const bool isbias = (int)blockIdx.x >= wblocks;
     const int kk2 = gm.k * gm.k;
     int wid = ((int)blockIdx.x - (isbias ? wblocks : 0)) * 4 + wv;
@@ -248,8 +225,8 @@ __global__ __launch_bounds__(kConvThreads) void convt_wgrad_kernel(const float *
     // the walk: rows x columns of the walked image, and the output position of a walked pixel (wy, wx) is (wy * st + offy, wx * st + offx)
     const int WH = isbias ? gm.OH : gm.H, WW = isbias ? gm.OW : gm.W, st = isbias ? 1 : gm.s;
     const int kh = tap / gm.k, offy = isbias ? 0 : kh - gm.pad, offx = isbias ? 0 : tap - kh * gm.k - gm.pad;
-    const int total = isbias ? Mo : M;
-    const int m_begin = chunk * kConvChunk, m_end = total - m_begin < kConvChunk ? total : m_begin + kConvChunk;
+    int m_begin, m_end;
+    chunk_range(chunk, isbias ? Mo : M, m_begin, m_end);
     int m = m_begin + half;
     int n = m / (WH * WW), wy = (m - n * (WH * WW)) / WW, wx = m - n * (WH * WW) - wy * WW;
     auto step = [&]() {
@@ -263,8 +240,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_wgrad_kernel(const float *
     const int ci = cit * 32 + j;                        // this lane's COLUMN of the B operand
     const bool civalid = ci < gm.Cin;
     f32x16 accA, accB;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) accA[r] = 0.0f, accB[r] = 0.0f;
+    tile_zero(accA), tile_zero(accB);
     int left = m_end - m;                               // steps of the chunk from this lane's next one on (it may fall below 0)
     auto fetch = [&](float (&gq)[kConvtDepth], float (&xq)[kConvtDepth], unsigned char (&fq)[kConvtDepth]) {
 #pragma unroll
@@ -290,11 +266,7 @@ __global__ __launch_bounds__(kConvThreads) void convt_wgrad_kernel(const float *
         fetch(gn, xn, fn);                               // the next group's (past the chunk's end: no load, +0)
 #pragma unroll
         for (int u = 0; u < kConvtDepth; ++u)
-            if (2 * u < todo) {
-                const bool first = fb[u] != 0;
-                accA = __builtin_amdgcn_mfma_f32_32x32x2f32(first ? gv[u] : 0.0f, xv[u], accA, 0, 0, 0);
-                accB = __builtin_amdgcn_mfma_f32_32x32x2f32(first ? 0.0f : gv[u], xv[u], accB, 0, 0, 0);
-            }
+            if (2 * u < todo) tile_mfma_selected(accA, accB, fb[u] != 0, gv[u], xv[u]);
 #pragma unroll
         for (int u = 0; u < kConvtDepth; ++u) gv[u] = gn[u], xv[u] = xn[u], fb[u] = fn[u];
     }
@@ -330,24 +302,13 @@ __global__ __launch_bounds__(kConvThreads) void convt_wgrad_finish_kernel(const 
 {
     const unsigned e = blockIdx.x * kConvThreads + threadIdx.x;
     if (e >= totalw + C2) return;
-    if (e < totalw) {
-        float acc = part[e];
-        for (int jc = 1; jc < chunks; ++jc) acc = acc + part[(size_t)jc * totalw + e];
-        gw[e] = acc;
-    } else {
-        const unsigned c2 = e - totalw;
-        float acc = partb[c2];
-        for (int jc = 1; jc < chunks_o; ++jc) acc = acc + partb[(size_t)jc * C2 + c2];
-        gb[c2] = acc;
-    }
+    if (e < totalw) gw[e] = chunk_sum(part, chunks, totalw, e);
+    else gb[e - totalw] = chunk_sum(partb, chunks_o, C2, e - totalw);
 }
 
 static int convt_check(const char *what, int N, int Cin, int H, int W, int C, int k, int s, int pad, int opad, ConvtGeom *gm)
 {
-    CTPVAE_REQUIRE(N >= 1 && Cin >= 1 && H >= 1 && W >= 1 && C >= 1, "%s: extents must be at least 1 (N=%d Cin=%d H=%d W=%d C=%d)", what, N,
-                   Cin, H, W, C);
-    CTPVAE_REQUIRE(k >= 1 && k <= kConvMaxK, "%s: the kernel size must be in 1 .. %d (got %d)", what, kConvMaxK, k);
-    CTPVAE_REQUIRE(s >= 1 && s <= k, "%s: the stride must be in 1 .. k (got s=%d k=%d)", what, s, k);
+    if (int rc = conv_check_common(what, N, Cin, H, W, C, k, s)) return rc;
     CTPVAE_REQUIRE(pad >= 0 && pad < k, "%s: the padding must be in 0 .. k - 1 (got pad=%d k=%d)", what, pad, k);
     CTPVAE_REQUIRE(opad >= 0 && opad < s, "%s: the output padding must be in 0 .. s - 1 (got opad=%d s=%d)", what, opad, s);
     const long long OH = ((long long)H - 1) * s - 2 * pad + k + opad, OW = ((long long)W - 1) * s - 2 * pad + k + opad, P = OH * OW;
@@ -363,12 +324,10 @@ static int convt_check(const char *what, int N, int Cin, int H, int W, int C, in
     return CTPVAE_OK;
 }
 
-static long long convt_tiles(long long n, int per) { return (n + per - 1) / per; }
-
 // chunks of the weight and of the bias gradient and the floats of their workspace; -1 when that count does not fit 31 bits
 static long long convt_wgrad_floats(const ConvtGeom &gm, int *chunks, int *chunks_o)
 {
-    const long long ch = convt_tiles((long long)gm.N * gm.HW, kConvChunk), cho = convt_tiles((long long)gm.N * gm.P, kConvChunk);
+    const long long ch = ceil_div((long long)gm.N * gm.HW, kConvChunk), cho = ceil_div((long long)gm.N * gm.P, kConvChunk);
     const long long fl = ch * gm.Cin * 2 * gm.C * gm.k * gm.k + cho * 2 * gm.C;
     *chunks = (int)ch, *chunks_o = (int)cho;
     return fl <= INT_MAX ? fl : -1;
@@ -397,9 +356,9 @@ int ctpvae_convt_fwd_f32(const float *x_dev, const float *w_dev, const float *b_
     CTPVAE_REQUIRE(x_dev && w_dev && b_dev && out_dev && first_out_dev, "convt_fwd: null pointer");
     ConvtGeom gm;
     if (int rc = convt_check("convt_fwd", N, Cin, H, W, C, k, s, pad, opad, &gm)) return rc;
-    const long long ctiles = convt_tiles(C, 32), pgroups = convt_tiles(convt_tiles(gm.OH, s) * convt_tiles(gm.OW, s), 128);
+    const long long ctiles = ceil_div(C, 32), pgroups = ceil_div(ceil_div(gm.OH, s) * ceil_div(gm.OW, s), 128);
     const long long blocks = (long long)N * ctiles * s * s * pgroups;
-    CTPVAE_REQUIRE(blocks <= INT_MAX, "convt_fwd: %lld workgroups do not fit 31 bits", blocks);
+    if (int rc = conv_check_blocks("convt_fwd", blocks)) return rc;
     hipLaunchKernelGGL(convt_fwd_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, x_dev, w_dev, b_dev, gm,
                        (int)ctiles, (int)pgroups, out_dev, first_out_dev);
     CTPVAE_LAUNCH_CHECK("convt_fwd_kernel");
@@ -416,10 +375,11 @@ int ctpvae_convt_bwd_weight_f32(const float *x_dev, const float *g_dev, const un
     int chunks, chunks_o;
     CTPVAE_REQUIRE(convt_wgrad_floats(gm, &chunks, &chunks_o) >= 0, "convt_bwd_weight: chunks * Cin * 2C * k * k + output chunks * 2C must fit "
                    "31 bits (chunks=%d and %d Cin=%d C=%d k=%d)", chunks, chunks_o, Cin, C, k);
-    const long long ctiles = convt_tiles(C, 32), citiles = convt_tiles(Cin, 32);
+    const long long ctiles = ceil_div(C, 32), citiles = ceil_div(Cin, 32);
     const long long wwaves = chunks * ctiles * citiles * k * k, bwaves = chunks_o * ctiles;
-    const long long wblocks = convt_tiles(wwaves, 4), blocks = wblocks + convt_tiles(bwaves, 4);
-    CTPVAE_REQUIRE(wwaves <= INT_MAX && blocks <= INT_MAX / 4, "convt_bwd_weight: %lld workgroups do not fit 31 bits", blocks);
+    const long long wblocks = ceil_div(wwaves, 4), blocks = wblocks + ceil_div(bwaves, 4);
+    // blocks * 4, the kernel's wave index, must fit too; wwaves and bwaves are below it
+    if (int rc = conv_check_blocks("convt_bwd_weight", blocks, INT_MAX / 4)) return rc;
     const unsigned totalw = (unsigned)Cin * 2u * (unsigned)C * (unsigned)(k * k);
     float *part = (float *)workspace_dev, *partb = part + (size_t)chunks * totalw;
     hipLaunchKernelGGL(convt_wgrad_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, x_dev, g_dev, first_dev, gm,
@@ -438,8 +398,8 @@ int ctpvae_convt_bwd_input_f32(const float *g_dev, const unsigned char *first_de
     CTPVAE_REQUIRE(g_dev && first_dev && w_dev && gx_out_dev, "convt_bwd_input: null pointer");
     ConvtGeom gm;
     if (int rc = convt_check("convt_bwd_input", N, Cin, H, W, C, k, s, pad, opad, &gm)) return rc;
-    const long long citiles = convt_tiles(Cin, 32), pgroups = convt_tiles(gm.HW, 128), blocks = (long long)N * citiles * pgroups;
-    CTPVAE_REQUIRE(blocks <= INT_MAX, "convt_bwd_input: %lld workgroups do not fit 31 bits", blocks);
+    const long long citiles = ceil_div(Cin, 32), pgroups = ceil_div(gm.HW, 128), blocks = (long long)N * citiles * pgroups;
+    if (int rc = conv_check_blocks("convt_bwd_input", blocks)) return rc;
     hipLaunchKernelGGL(convt_dgrad_kernel, dim3((unsigned)blocks), dim3(kConvThreads), 0, (hipStream_t)stream, g_dev, first_dev, w_dev, gm,
                        (int)citiles, (int)pgroups, gx_out_dev);
     CTPVAE_LAUNCH_CHECK("convt_dgrad_kernel");

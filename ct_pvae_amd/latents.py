@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
@@ -44,14 +45,7 @@ def latent_draws(n, length, *, ns, seed, draw, level, first_object=0):
 
 
 def _check_input(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"normal_latents: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"normal_latents: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.numel() == 0:
-        raise ValueError(f"normal_latents: {name} must be [B][channels][H][W], the encoder's layout (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"normal_latents: {name} must be contiguous (got strides {tuple(t.stride())})")
+    check_float32("normal_latents", name, t, 4, "[B][channels][H][W], the encoder's layout")
 
 
 class _NormalLatents(torch.autograd.Function):

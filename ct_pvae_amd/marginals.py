@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
@@ -67,15 +68,8 @@ def bin_samples(samples, lo, width, bins):
 
 
 def _check_input(name, t, shape_xy):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"PixelMarginals.add: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"PixelMarginals.add: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.shape[1] != 1 or t.numel() == 0 or tuple(t.shape[2:]) != shape_xy:
-        raise ValueError(f"PixelMarginals.add: {name} must be [n][1][{shape_xy[0]}][{shape_xy[1]}], the decoder's layout "
-                         f"(got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"PixelMarginals.add: {name} must be contiguous (got strides {tuple(t.stride())})")
+    check_float32("PixelMarginals.add", name, t, 4, f"[n][1][{shape_xy[0]}][{shape_xy[1]}], the decoder's layout",
+                  lambda shape: shape[1] == 1 and tuple(shape[2:]) == shape_xy)
 
 
 class PixelMarginals:

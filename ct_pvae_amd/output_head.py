@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
+from ._args import check_float32
 from .forward_functions import _stream_ptr
 
 __all__ = ["truncated_normal_head", "head_uniforms"]
@@ -38,14 +39,7 @@ def head_uniforms(n, pix, *, seed, draw, first_object=0):
 
 
 def _check_input(name, t):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"truncated_normal_head: {name} must be a torch tensor (got {type(t).__name__})")
-    if t.dtype is not torch.float32:
-        raise TypeError(f"truncated_normal_head: {name} must be float32 (got {t.dtype})")
-    if t.dim() != 4 or t.shape[1] != 1 or t.numel() == 0:
-        raise ValueError(f"truncated_normal_head: {name} must be [n][1][X][Y], the decoder's layout (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise ValueError(f"truncated_normal_head: {name} must be contiguous (got strides {tuple(t.stride())})")
+    check_float32("truncated_normal_head", name, t, 4, "[n][1][X][Y], the decoder's layout", lambda shape: shape[1] == 1)
 
 
 class _TruncatedNormalHead(torch.autograd.Function):
