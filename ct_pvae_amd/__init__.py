@@ -10,12 +10,12 @@ from .helper_functions import (calculate_log_prob_M_given_R, create_sinogram, cr
 from .create_masks import create_all_masks  # noqa: F401
 from .fbp import iradon, iradon_all  # noqa: F401
 from .recon import crop, evaluate_sinogram, recon, siddon_backproject  # noqa: F401
-from .mcmc import hmc_sample  # noqa: F401
+from .mcmc import HmcMarginals, hmc_marginals, hmc_sample, split_rhat  # noqa: F401
 from .beta_head import beta_head, beta_head_words  # noqa: F401
 from .beta_latents import beta_latent_words, beta_latents  # noqa: F401
 from .output_head import head_uniforms, truncated_normal_head  # noqa: F401
 from .latents import latent_draws, normal_latents  # noqa: F401
-from .marginals import PixelMarginals, bin_samples  # noqa: F401
+from .marginals import PixelMarginals, bin_samples, hist_distance  # noqa: F401
 from .convblock import dropout, dropout_mask, dropout_pad, maxout, periodic_pad  # noqa: F401
 from .conv import periodic_conv_maxout  # noqa: F401
 from .conv_transpose import conv_transpose_maxout  # noqa: F401

@@ -12,6 +12,7 @@ same code on the Beta head's samples).
     m.count, m.hist, m.mean(), m.std(), m.edges, m.save(path), PixelMarginals.load(path)
     bin_samples(samples, lo, width, bins)                                       the same bin rule on any [..., pix] host array (e.g.
                                                                                 hmc_sample's output), so two curves share their bins
+    hist_distance(a, b)                                                         total-variation distance per pixel of two hist
 
 Nothing in add() grows with `draws`: beside alpha, beta and the state it allocates one workspace of at most 1024 * X * Y bytes.
 There is no CPU path for add()."""
@@ -25,7 +26,7 @@ from ._args import check_float32
 from .forward_functions import _stream_ptr
 from .output_head import _counter_args
 
-__all__ = ["PixelMarginals", "bin_samples", "bin_columns", "MAX_BINS"]
+__all__ = ["PixelMarginals", "bin_samples", "bin_columns", "hist_distance", "MAX_BINS"]
 
 MAX_BINS = 254     # CTPVAE_MARGINALS_MAX_BINS
 HEADS = {"truncated_normal": "tn_marginals", "beta": "beta_marginals"}     # head -> the stem of its two entry points
@@ -65,6 +66,18 @@ def bin_samples(samples, lo, width, bins):
     pix, cols = col.shape[1], int(bins) + 2
     flat = (np.arange(pix, dtype=np.int64)[None, :] * cols + col).ravel()
     return np.bincount(flat, minlength=pix * cols).astype(np.int64).reshape(pix, cols)
+
+
+def hist_distance(a, b):
+    """float64 [pix]: the total-variation distance 0.5 * sum_col |a / sum(a) - b / sum(b)| between two binned marginals, integer
+    arrays [pix][cols] of one shape (two hist of one grid: a PixelMarginals' against an HmcMarginals' object).  A row with an empty
+    total gives NaN."""
+    a, b = (np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in (a, b))
+    if a.ndim != 2 or a.shape != b.shape or a.dtype.kind not in "iu" or b.dtype.kind not in "iu":
+        raise ValueError(f"hist_distance: two integer arrays [pix][cols] of one shape (got {a.shape} {a.dtype}, {b.shape} {b.dtype})")
+    a, b = a.astype(np.float64), b.astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 0.5 * np.abs(a / a.sum(1, keepdims=True) - b / b.sum(1, keepdims=True)).sum(1)
 
 
 def _check_input(name, t, shape_xy):

@@ -694,6 +694,32 @@ int ctpvae_hmc_run_f32(float *state_dev, int C, unsigned first_chain, int chains
                        unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev, float *lar_out_dev,
                        float *accepted_out_dev, float *target_out_dev, ctpvae_stream_t stream);
 
+/* ---- the HMC sampler with the chains' per-pixel marginals accumulated inside the launch (csrc/hmc_marginals.hip states the layout and
+ * the orders): the transitions of ctpvae_hmc_run_f32 bit for bit -- same arguments, same state (ctpvae_hmc_init_f32 starts it), same
+ * random numbers -- and, for every kept step (index >= n_keep_from) and pixel k < K, with O the sample _run_f32 would store:
+ *   hist_dev [B][K][bins + 2] int64: + 1 in the column of O under the bin rule of ctpvae_tn_marginals_f32 (t = (O - lo) / width in
+ *     fp32; column 0 if !(t >= 0), NaN too; bins + 1 if t >= bins; else 1 + (int)t), pooled over the chains of object c /
+ *     chains_per_object; rows as in the P-VAE's marginals, 1 <= bins <= CTPVAE_MARGINALS_MAX_BINS.  Integer atomics: any order, same bits.
+ *   mom_dev [2][2][C][K] float64: [h][0] += (double)O and [h][1] += (double)O * (double)O, h = 0 for steps with index < n_half_from
+ *     and 1 from there on.  Each sum is strictly sequential over the chain's own steps in ascending order, however the run is cut into
+ *     launches; a chain's sums do not depend on the other chains.
+ *   accepted_dev [C] int64: + 1 per accepted kept step.
+ * A launch ADDS to the three arrays: zero them before the first (8-byte aligned, never NULL).  samples_out_dev, lar_out_dev,
+ * accepted_out_dev, target_out_dev: all four as in _run_f32, or all four NULL -- then nothing is stored per step and no argument's
+ * size depends on the number of steps; any other mix is refused.  n_steps is 1 .. CTPVAE_HMC_MAX_STEPS here too: the longest launch
+ * of the shape that sizes that cap (8 x 8, 180 angles, 512 steps) with bins = 254 takes 78.9 ms on the MI355X, under 100 ms
+ * (profiles/hmc_marginals_timing.txt; _run_f32's: 76.4 ms).
+ *   _marginals_lds_bytes(N, A, bins): dynamic LDS of one workgroup (host only): the sampler's tables plus K * (bins + 2) * 4 bytes of
+ *     counts, at most 121 KiB (8 x 8, 256 angles, 254 bins); the entry point raises the kernel's limit above the default 64 KiB. */
+long long ctpvae_hmc_marginals_lds_bytes(int N, int A, int bins);
+int ctpvae_hmc_run_marginals_f32(float *state_dev, int C, unsigned first_chain, int chains_per_object, int N, const float *T8_dev,
+                                 const float *Tinv8_dev, int A, const float *mask_dev, const float *meas_dev, float pnm, int M,
+                                 const float *logw_dev, const float *alpha_dev, const float *lbeta_dev, int L, int n_steps,
+                                 unsigned n_keep_from, unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev,
+                                 float *lar_out_dev, float *accepted_out_dev, float *target_out_dev, unsigned n_half_from, float lo,
+                                 float width, int bins, long long *hist_dev, double *mom_dev, long long *accepted_dev,
+                                 ctpvae_stream_t stream);
+
 /* ---- the P-VAE decoder's TruncatedNormal output head (ctvae/helper_functions.py:198-201, :273): sample, log-density and its
  * per-object sum in ONE launch, their gradients in one more (csrc/head.hip states the function, the order of the sum and the layout
  * of the random numbers).  alpha_dev, beta_dev [n][pix]: the decoder's raw outputs, pix = X * Y pixels per object, fp32.
