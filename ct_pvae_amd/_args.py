@@ -1,4 +1,5 @@
-"""The one check of a float32 tensor argument that every fused operator makes before it looks at a device."""
+"""The checks every fused operator makes before it looks at a device: of a float32 tensor argument, and of the counter words (seed,
+draw, first_object) of the operators that draw random numbers."""
 import torch
 
 
@@ -13,3 +14,13 @@ def check_float32(what, name, t, dim, layout, shape_ok=None):
         raise ValueError(f"{what}: {name} must be {layout} (got {tuple(t.shape)})")
     if not t.is_contiguous():
         raise ValueError(f"{what}: {name} must be contiguous (got strides {tuple(t.stride())})")
+
+
+def counter_args(seed, draw, first_object):
+    """(seed, draw, first_object) as the library takes them: the seed's low 64 bits, one 32-bit draw word, a non-negative offset."""
+    seed, draw, first_object = int(seed), int(draw), int(first_object)
+    if not 0 <= draw < 2 ** 32:
+        raise ValueError(f"draw is one 32-bit counter word: 0 <= draw < 2^32 (got {draw})")
+    if not 0 <= first_object < 2 ** 63:
+        raise ValueError(f"first_object must be >= 0 (got {first_object})")
+    return seed & (2 ** 64 - 1), draw, first_object

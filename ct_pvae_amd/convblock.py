@@ -24,9 +24,8 @@ import numpy as np
 import torch
 
 from . import _lib, forward_functions
-from ._args import check_float32
+from ._args import check_float32, counter_args
 from .forward_functions import _stream_ptr
-from .output_head import _counter_args
 
 __all__ = ["periodic_pad", "maxout", "dropout", "dropout_pad", "dropout_mask"]
 
@@ -103,7 +102,7 @@ def _rate_args(what, rate):
 
 
 def _key_args(what, seed, draw, layer, first_object, n, length):
-    seed, draw, first_object = _counter_args(seed, draw, first_object)
+    seed, draw, first_object = counter_args(seed, draw, first_object)
     layer = int(layer)
     if not 0 <= layer < 2 ** 24:
         raise ValueError(f"{what}: layer shares a counter word with the tag: 0 <= layer < 2^24 (got {layer})")

@@ -87,11 +87,8 @@ struct BetaPrep {
 __device__ __forceinline__ BetaPrep beta_prep(float alpha, float beta)
 {
     BetaPrep r;
-    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
-    r.a = alpha >= 1.0f ? alpha : ea + kHeadEps;
-    r.b = beta >= 1.0f ? beta : eb + kHeadEps;
-    r.da = alpha >= 1.0f ? 1.0f : ea;
-    r.db = beta >= 1.0f ? 1.0f : eb;
+    r.a = positive_range(alpha, r.da);
+    r.b = positive_range(beta, r.db);
     r.g0 = beta_gamma_prep(r.a);
     r.g1 = beta_gamma_prep(r.b);
     return r;

@@ -4,7 +4,7 @@
 // the log-densities; the backward gives what TensorFlow's tape gives on that composition.
 //
 // The function, per pixel, fp32 (EPS = FLT_EPSILON; sr = sqrt_reg, an argument, 0 < sr < 0.5; hi = 1 - sr in fp32):
-//   pr(t) = t >= 1 ? t : exp(t - 1) + EPS;      a = pr(alpha), b = pr(beta)                                  (tn_head.h's pr)
+//   pr(t) = t >= 1 ? t : exp(t - 1) + EPS;      a = pr(alpha), b = pr(beta)                       (quad_io.h's positive_range)
 //   for the two gammas j = 0 (c = a) and j = 1 (c = b):
 //       cb = c < 1 ? c + 1 : c;   d = cb - 1/3;   s = 1 / sqrt(9 d)                         (Marsaglia-Tsang, boosted below 1)
 //       attempts k = 0 .. 15:   block = Philox4x32-10((lo32(e), hi32(e), draw, kBetaTag | j << 8 | k), key = seed)
@@ -46,92 +46,53 @@
 // first_object draws what the whole batch draws.  kBetaTag = 0x42000000u (in use elsewhere: 0x544E48, 0x484D43, 0x4C000000 | ..,
 // 0x44000000 | .., 0x51000000 | .. -- beta_latent.hip's, which runs this sampler under its own fourth counter word --, 0).
 //
-// Layout and the order of the per-object sum: head.hip's, through quad_io.h -- one workgroup of 1024 threads per object, no atomics:
-//   quad q = pixels 4q .. 4q+3:  s_q = ((lp_4q + lp_4q+1) + lp_4q+2) + lp_4q+3                        (pixels past pix add +0.0f)
-//   thread t takes the quads t, t + 1024, ...:  acc_t = ((0 + s_t) + s_(t+1024)) + ...                 (a thread without a quad: +0.0f)
-//   wave w: W_w = wave_sum(acc) (the xor butterfly 32, 16, 8, 4, 2, 1);   LP[o] = ((W_0 + W_1) + W_2) + ... + W_15
-// so LP[o] has the same bits whatever n, first_object and the object's alignment in memory are.  The backward has no sum: it walks
-// the n * pix pixels as memory quads, 256 threads per workgroup.
+// Layout and the order of the per-object sum LP[o]: quad_io.h states them (head_fwd_body, head_bwd_body) -- one workgroup of 1024
+// threads per object, no atomics, the same bits whatever n, first_object and the object's alignment in memory are; the backward has
+// no sum and walks the n * pix pixels as memory quads, 256 threads per workgroup.
 //
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): no scratch, no spills in either kernel; the occupancy is stated
-// next to each kernel.
+// Resources: no scratch and no VGPR spills in either kernel, 5 waves per SIMD each (profiles/sampling_refactor_resources.txt); a forward
+// workgroup is 4 waves per SIMD, so one per CU at a time; the backward runs five 256-thread workgroups per CU.
 #include "beta_head.h"
 
 namespace ctpvae {
 
 static_assert(kBetaTag == 0x42000000u, "kBetaTag = 0x42000000u is part of the stream's definition (include/ctpvae_radon.h)");
-constexpr int kBetaFwdThreads = kObjectSumThreads;
-constexpr int kBetaBwdThreads = 256;
 
-struct BetaRng {
-    unsigned long long first_pixel;   // first_object * pix
-    unsigned draw, k0, k1;
-};
-
-// 90 VGPRs, no scratch: 5 waves per SIMD by registers; a workgroup is 4 waves per SIMD, so one workgroup per CU at a time
-__global__ __launch_bounds__(kBetaFwdThreads) void beta_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                                        int pix, BetaRng rng, float sr, int ptr_aligned,
-                                                                        float *__restrict__ x_out, float *__restrict__ lp_sum,
-                                                                        float *__restrict__ lp_elem, float *__restrict__ aux)
+__global__ __launch_bounds__(kObjectSumThreads) void beta_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+                                                                          int pix, QuadRng rng, float sr, int ptr_aligned,
+                                                                          float *__restrict__ x_out, float *__restrict__ lp_sum,
+                                                                          float *__restrict__ lp_elem, float *__restrict__ aux)
 {
-    __shared__ float wsum[kBetaFwdThreads / 64];
-    const int o = blockIdx.x, t = threadIdx.x;
-    const size_t base = (size_t)o * pix;
-    const bool vec = ptr_aligned != 0 && (base & 3) == 0;
-    const int quads = (pix + 3) >> 2;
-    float acc = 0.0f;
-    for (int q = t; q < quads; q += kBetaFwdThreads) {
-        const int r = 4 * q;
-        const int cnt = pix - r < 4 ? pix - r : 4;
-        const size_t i = base + r;
-        float al[4], be[4], x[4], lp[4];
-        quad_load(alpha, i, cnt, vec, 1.0f, al);
-        quad_load(beta, i, cnt, vec, 1.0f, be);
+    head_fwd_body(alpha, beta, pix, ptr_aligned, x_out, lp_sum, lp_elem,
+                  [&](const float (&al)[4], const float (&be)[4], size_t i, int cnt, bool, float (&x)[4], float (&lp)[4]) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const BetaPixel px = beta_pixel<false>(al[j], be[j], rng.first_pixel + i + j, rng.draw, rng.k0, rng.k1, sr);
-            x[j] = px.x;
-            lp[j] = j < cnt ? px.lp : 0.0f;
-            if (aux != nullptr && j < cnt) {
-                float *w = aux + 8 * (i + j);
-                w[0] = px.g0.zn, w[1] = px.g0.ub, w[2] = (float)px.g0.k, w[3] = px.g0.lg;
-                w[4] = px.g1.zn, w[5] = px.g1.ub, w[6] = (float)px.g1.k, w[7] = px.g1.lg;
-            }
-        }
-        quad_store(x_out, i, cnt, vec, x);
-        if (lp_elem != nullptr) quad_store(lp_elem, i, cnt, vec, lp);
-        acc += ((lp[0] + lp[1]) + lp[2]) + lp[3];
-    }
-    const float s = object_sum_1024(acc, wsum, t);
-    if (t == 0) lp_sum[o] = s;
+                      for (int j = 0; j < 4; ++j) {
+                          const BetaPixel px = beta_pixel<false>(al[j], be[j], rng.first + i + j, rng.draw, rng.k0, rng.k1, sr);
+                          x[j] = px.x, lp[j] = px.lp;
+                          if (aux != nullptr && j < cnt) {
+                              float *w = aux + 8 * (i + j);
+                              w[0] = px.g0.zn, w[1] = px.g0.ub, w[2] = (float)px.g0.k, w[3] = px.g0.lg;
+                              w[4] = px.g1.zn, w[5] = px.g1.ub, w[6] = (float)px.g1.k, w[7] = px.g1.lg;
+                          }
+                      }
+                  });
 }
 
-// 93 VGPRs, no scratch: 5 waves per SIMD, i.e. five 256-thread workgroups per CU (the float64 loops diverge per lane: occupancy hides them)
-__global__ __launch_bounds__(kBetaBwdThreads) void beta_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                                        long long total, int pix, BetaRng rng, float sr, int ptr_aligned,
+// (the float64 loops diverge per lane: occupancy hides them)
+__global__ __launch_bounds__(kQuadBwdThreads) void beta_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+                                                                        long long total, int pix, QuadRng rng, float sr, int ptr_aligned,
                                                                         const float *__restrict__ g_x, const float *__restrict__ g_lp,
                                                                         float *__restrict__ g_alpha, float *__restrict__ g_beta)
 {
-    const long long i0 = 4 * ((long long)blockIdx.x * kBetaBwdThreads + threadIdx.x);
-    if (i0 >= total) return;
-    const int cnt = total - i0 < 4 ? (int)(total - i0) : 4;
-    const size_t i = (size_t)i0;
-    const bool vec = ptr_aligned != 0;
-    float al[4], be[4], gx[4], ga[4], gb[4];
-    quad_load(alpha, i, cnt, vec, 1.0f, al);
-    quad_load(beta, i, cnt, vec, 1.0f, be);
-    if (g_x != nullptr) quad_load(g_x, i, cnt, vec, 0.0f, gx);
-    else gx[0] = gx[1] = gx[2] = gx[3] = 0.0f;
+    head_bwd_body(alpha, beta, total, pix, ptr_aligned, g_x, g_lp, g_alpha, g_beta,
+                  [&](const float (&al)[4], const float (&be)[4], size_t i, int, bool, const float (&gx)[4], const float (&G)[4],
+                      float (&ga)[4], float (&gb)[4]) {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        // the pixel's object: total < 2^31, so 32-bit division (pixels past the end read object n - 1 and are not stored)
-        const unsigned e = (unsigned)(j < cnt ? i0 + j : i0);
-        const float G = g_lp != nullptr ? g_lp[e / (unsigned)pix] : 0.0f;
-        const BetaPixel px = beta_pixel<true>(al[j], be[j], rng.first_pixel + i + j, rng.draw, rng.k0, rng.k1, sr);
-        beta_pixel_grad(px, gx[j], G, ga[j], gb[j]);
-    }
-    quad_store(g_alpha, i, cnt, vec, ga);
-    quad_store(g_beta, i, cnt, vec, gb);
+                      for (int j = 0; j < 4; ++j) {
+                          const BetaPixel px = beta_pixel<true>(al[j], be[j], rng.first + i + j, rng.draw, rng.k0, rng.k1, sr);
+                          beta_pixel_grad(px, gx[j], G[j], ga[j], gb[j]);
+                      }
+                  });
 }
 
 }  // namespace ctpvae
@@ -146,9 +107,9 @@ int ctpvae_beta_head_fwd_f32(const float *alpha_dev, const float *beta_dev, int 
 {
     if (int rc = beta_head_check("beta_head_fwd", alpha_dev, beta_dev, n, pix, first_object, sqrt_reg)) return rc;
     CTPVAE_REQUIRE(x_out_dev && lp_sum_out_dev, "beta_head_fwd: null output pointer");
-    const BetaRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32)};
+    const QuadRng rng = quad_rng(first_object, pix, seed, draw);
     const int aligned = head_aligned16({alpha_dev, beta_dev, x_out_dev, lp_elem_out_dev}) ? 1 : 0;
-    hipLaunchKernelGGL(beta_head_fwd_kernel, dim3(n), dim3(kBetaFwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, pix, rng,
+    hipLaunchKernelGGL(beta_head_fwd_kernel, dim3(n), dim3(kObjectSumThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, pix, rng,
                        sqrt_reg, aligned, x_out_dev, lp_sum_out_dev, lp_elem_out_dev, aux_out_dev);
     CTPVAE_LAUNCH_CHECK("beta_head_fwd_kernel");
     return CTPVAE_OK;
@@ -160,12 +121,10 @@ int ctpvae_beta_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int 
 {
     if (int rc = beta_head_check("beta_head_bwd", alpha_dev, beta_dev, n, pix, first_object, sqrt_reg)) return rc;
     CTPVAE_REQUIRE(g_alpha_out_dev && g_beta_out_dev, "beta_head_bwd: null output pointer");
-    const BetaRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32)};
+    const QuadRng rng = quad_rng(first_object, pix, seed, draw);
     const int aligned = head_aligned16({alpha_dev, beta_dev, g_x_dev, g_alpha_out_dev, g_beta_out_dev}) ? 1 : 0;
     const long long total = (long long)n * pix;
-    const long long per_block = 4ll * kBetaBwdThreads;
-    const unsigned grid = (unsigned)((total + per_block - 1) / per_block);
-    hipLaunchKernelGGL(beta_head_bwd_kernel, dim3(grid), dim3(kBetaBwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, total, pix, rng,
+    hipLaunchKernelGGL(beta_head_bwd_kernel, dim3(head_bwd_grid(total)), dim3(kQuadBwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, total, pix, rng,
                        sqrt_reg, aligned, g_x_dev, g_lp_dev, g_alpha_out_dev, g_beta_out_dev);
     CTPVAE_LAUNCH_CHECK("beta_head_bwd_kernel");
     return CTPVAE_OK;
@@ -175,17 +134,13 @@ int ctpvae_beta_head_words_host_u32(int n, int pix, long long first_object, unsi
                                     int attempt, unsigned *out_host)
 {
     CTPVAE_REQUIRE(out_host, "beta_head_words_host: null pointer");
-    CTPVAE_REQUIRE(n > 0 && pix > 0, "beta_head_words_host: sizes must be positive (n=%d pix=%d)", n, pix);
-    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "beta_head_words_host: n * pix must fit 31 bits (n=%d pix=%d)", n, pix);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
-                   "beta_head_words_host: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", first_object);
+    if (int rc = head_size_check("beta_head_words_host", n, pix, first_object)) return rc;
     CTPVAE_REQUIRE(gamma >= 0 && gamma <= 1 && attempt >= 0 && attempt < kBetaAttempts,
                    "beta_head_words_host: gamma must be 0 or 1 and 0 <= attempt < 16 (got %d, %d)", gamma, attempt);
-    const unsigned long long e0 = (unsigned long long)first_object * (unsigned long long)pix;
+    const QuadRng rng = quad_rng(first_object, pix, seed, draw);
     const long long total = (long long)n * pix;
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     for (long long i = 0; i < total; ++i) {
-        const Philox4 b = beta_block(e0 + (unsigned long long)i, draw, (unsigned)gamma, (unsigned)attempt, k0, k1);
+        const Philox4 b = beta_block(rng.first + (unsigned long long)i, draw, (unsigned)gamma, (unsigned)attempt, rng.k0, rng.k1);
         for (int w = 0; w < 4; ++w) out_host[4 * i + w] = b.w[w];
     }
     return CTPVAE_OK;

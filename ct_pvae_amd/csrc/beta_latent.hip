@@ -6,7 +6,7 @@
 // Input: skip [B][2C][H][W], contiguous, the encoder's output at the level (latent.hip's layout).  Channels 0 .. C-1 are loc,
 // C .. 2C-1 are log_scale: with len = C H W, object b's loc is at b * 2 len and its log_scale at b * 2 len + len.  Per element i of
 // object b (EPS = FLT_EPSILON; there is no + sqrt_reg: the reference writes Beta(positive_range(loc), positive_range(log_scale))):
-//   pr(t) = t >= 1 ? t : exp(t - 1) + EPS;   a = pr(loc),  b1 = pr(log_scale)                                   (tn_head.h's pr, fp32)
+//   pr(t) = t >= 1 ? t : exp(t - 1) + EPS;   a = pr(loc),  b1 = pr(log_scale)                        (quad_io.h's positive_range, fp32)
 //   sample s = 0 .. ns-1:  lg_0, lg_1 = beta_log_gamma(a), beta_log_gamma(b1)       (beta_head.h; beta_head.hip states the sampler)
 //       z[s * B + b][i] = 1 / (1 + exp(lg_1 - lg_0))      (sample-major: the layout the decoder is fed; not clamped, may round to 0 or 1)
 //       y               = 1 / (1 + exp(lg_0 - lg_1))      (1 - z without cancellation; the backward's)
@@ -30,11 +30,8 @@
 // on ns.  Top bytes of the fourth counter word in use: beta_head.hip's header keeps the list.
 //
 // Work split of the forward (one launch, 1024 threads per workgroup):
-//   * the first B workgroups (only when a KL output is asked for) each sum ONE object's KL in quad_io.h's fixed order:
-//       quad q = elements 4q .. 4q+3:  s_q = ((kl_4q + kl_4q+1) + kl_4q+2) + kl_4q+3                     (elements past len add +0.0f)
-//       thread t takes the quads t, t + 1024, ...:  acc_t = ((0 + s_t) + s_(t+1024)) + ...               (a thread without a quad: +0.0f)
-//       KL[b] = ((W_0 + W_1) + W_2) + ... + W_15,  W_w = wave_sum(acc) of wave w                         (object_sum_1024)
-//     so KL[b] has the same bits whatever B, first_object and the object's alignment in memory are;
+//   * the first B workgroups (only when a KL output is asked for) each sum ONE object's KL in the fixed order that quad_io.h states
+//     (latent_kl_walk), so KL[b] has the same bits whatever B, first_object and the object's alignment in memory are;
 //   * the ns * B * ceil(len / 1024) workgroups behind them draw the samples, ONE ELEMENT per thread: a sample costs two gammas of
 //     (Philox, ndtri, three logf) per attempt and needs no sum, so the samples are spread over as many waves as there are elements
 //     instead of queueing behind B workgroups (at 4 bytes per lane the accesses still coalesce; arithmetic bounds this part, not
@@ -46,23 +43,15 @@
 namespace ctpvae {
 
 static_assert(kBetaLatentTag == 0x51000000u, "kBetaLatentTag = 0x51000000u is part of the stream's definition (include/ctpvae_radon.h)");
-constexpr int kBetaLatentFwdThreads = kObjectSumThreads;
-constexpr int kBetaLatentBwdThreads = 256;
 constexpr int kBetaLatentMaxNs = 2048;
 constexpr double kLnPi = 1.1447298858494001741434273513531;
 
+// QuadRng's words with the level between them, not behind: in this order beta_latent_bwd_kernel's code is what it was before the
+// walks were shared, instruction for instruction
 struct BetaLatentRng {
-    unsigned long long first_elem;   // first_object * len
+    unsigned long long first;        // first_object * len
     unsigned draw, level, k0, k1;
 };
-
-// tn_head.h's positive_range and its slope
-__device__ __forceinline__ float beta_latent_pr(float t, float &slope)
-{
-    const float e = expf(t - 1.0f);
-    slope = t >= 1.0f ? 1.0f : e;
-    return t >= 1.0f ? t : e + kHeadEps;
-}
 
 // kl of one element in float64 on the fp32 concentrations, rounded once
 __device__ __forceinline__ float beta_latent_kl(float a32, float b32)
@@ -77,52 +66,34 @@ __device__ __forceinline__ float beta_latent_kl(float a32, float b32)
     return (float)v;
 }
 
-// 58 VGPRs, no scratch: 7 waves per SIMD by registers; a workgroup is 4 waves per SIMD, so one workgroup per CU at a time
-__global__ __launch_bounds__(kBetaLatentFwdThreads) void beta_latent_fwd_kernel(const float *__restrict__ skip, int B, int len, int chunks,
-                                                                                int kl_blocks, BetaLatentRng rng, int ptr_aligned,
-                                                                                float *__restrict__ z_out, float *__restrict__ kl_sum,
-                                                                                float *__restrict__ kl_elem, float *__restrict__ aux)
+// a workgroup is 4 waves per SIMD, so one workgroup per CU at a time (registers: profiles/sampling_refactor_resources.txt)
+__global__ __launch_bounds__(kObjectSumThreads) void beta_latent_fwd_kernel(const float *__restrict__ skip, int B, int len, int chunks,
+                                                                            int kl_blocks, BetaLatentRng rng, int ptr_aligned,
+                                                                            float *__restrict__ z_out, float *__restrict__ kl_sum,
+                                                                            float *__restrict__ kl_elem, float *__restrict__ aux)
 {
-    __shared__ float wsum[kBetaLatentFwdThreads / 64];
     const int t = threadIdx.x;
     const size_t L = (size_t)len;
-    if ((int)blockIdx.x < kl_blocks) {                 // ---- the KL of object b (workgroup-uniform branch: the barrier below is safe)
-        const int b = blockIdx.x;
-        const size_t loc0 = 2 * (size_t)b * L, ls0 = loc0 + L, el0 = (size_t)b * L;
-        const bool al = ptr_aligned != 0;
-        const bool vec_loc = al && (loc0 & 3) == 0, vec_ls = al && (ls0 & 3) == 0, vec_el = al && (el0 & 3) == 0;
-        const int quads = (len >> 2) + ((len & 3) != 0);
-        float acc = 0.0f;
-        for (int q = t; q < quads; q += kBetaLatentFwdThreads) {
-            const int r = 4 * q;
-            const int cnt = len - r < 4 ? len - r : 4;
-            float loc[4], ls[4], kl[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            quad_load(skip, loc0 + r, cnt, vec_loc, 1.0f, loc);
-            quad_load(skip, ls0 + r, cnt, vec_ls, 1.0f, ls);
-            // the four elements' float64 chains are independent and branch-free: unrolled, they overlap each other's latencies
+    if ((int)blockIdx.x < kl_blocks) {                 // ---- the KL of object b (workgroup-uniform branch: the walk's barrier is safe)
+        // the four elements' float64 chains are independent and branch-free: unrolled, they overlap each other's latencies
+        latent_kl_walk(skip, blockIdx.x, len, ptr_aligned, 1.0f, kl_sum, kl_elem,
+                       [](const LatentRows &, int, int, const float (&loc)[4], const float (&ls)[4], float (&kl)[4]) {
+                           float unused;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float unused;
-                const float v = beta_latent_kl(beta_latent_pr(loc[j], unused), beta_latent_pr(ls[j], unused));
-                kl[j] = j < cnt ? v : 0.0f;
-            }
-            if (kl_elem != nullptr) quad_store(kl_elem, el0 + r, cnt, vec_el, kl);
-            acc += ((kl[0] + kl[1]) + kl[2]) + kl[3];
-        }
-        const float total = object_sum_1024(acc, wsum, t);
-        if (t == 0 && kl_sum != nullptr) kl_sum[b] = total;
+                           for (int j = 0; j < 4; ++j) kl[j] = beta_latent_kl(positive_range(loc[j], unused), positive_range(ls[j], unused));
+                       });
         return;
     }
     // ---- the samples: workgroup (row = s * B + b, chunk), one element per thread
     const unsigned w = blockIdx.x - (unsigned)kl_blocks;
     const unsigned row = w / (unsigned)chunks;
-    const int i = (int)(w - row * (unsigned)chunks) * kBetaLatentFwdThreads + t;
+    const int i = (int)(w - row * (unsigned)chunks) * kObjectSumThreads + t;
     if (i >= len) return;
     const unsigned s = row / (unsigned)B, b = row - s * (unsigned)B;
     float unused;
-    const float a = beta_latent_pr(skip[2 * (size_t)b * L + i], unused);
-    const float b1 = beta_latent_pr(skip[2 * (size_t)b * L + L + i], unused);
-    const unsigned long long e = rng.first_elem + (size_t)b * L + i;
+    const float a = positive_range(skip[2 * (size_t)b * L + i], unused);
+    const float b1 = positive_range(skip[2 * (size_t)b * L + L + i], unused);
+    const unsigned long long e = rng.first + (size_t)b * L + i;
     const BetaGamma g0 = beta_log_gamma(a, e, rng.draw, beta_latent_word3(rng.level, s, 0u), rng.k0, rng.k1);
     const BetaGamma g1 = beta_log_gamma(b1, e, rng.draw, beta_latent_word3(rng.level, s, 1u), rng.k0, rng.k1);
     const size_t o = (size_t)row * L + i;
@@ -134,33 +105,28 @@ __global__ __launch_bounds__(kBetaLatentFwdThreads) void beta_latent_fwd_kernel(
     }
 }
 
-// 145 VGPRs, no scratch: 3 waves per SIMD, i.e. three 256-thread workgroups per CU (the float64 loops diverge per lane; the two
-// beta_dlg bodies and the sampler's state are what the registers hold)
-__global__ __launch_bounds__(kBetaLatentBwdThreads) void beta_latent_bwd_kernel(const float *__restrict__ skip, int B, int len, int ns,
-                                                                                BetaLatentRng rng, int ptr_aligned, int blocks_per_object,
-                                                                                const float *__restrict__ g_z, const float *__restrict__ g_kl,
-                                                                                float *__restrict__ g_skip)
+// 3 waves per SIMD, i.e. three 256-thread workgroups per CU (profiles/sampling_refactor_resources.txt; the float64 loops diverge per
+// lane; the two beta_dlg bodies and the sampler's state are what the registers hold)
+__global__ __launch_bounds__(kQuadBwdThreads) void beta_latent_bwd_kernel(const float *__restrict__ skip, int B, int len, int ns,
+                                                                          BetaLatentRng rng, int ptr_aligned, int blocks_per_object,
+                                                                          const float *__restrict__ g_z, const float *__restrict__ g_kl,
+                                                                          float *__restrict__ g_skip)
 {
-    const int b = blockIdx.x / blocks_per_object;
-    const int q = (blockIdx.x - b * blocks_per_object) * kBetaLatentBwdThreads + threadIdx.x;
-    if (q >= (len >> 2) + ((len & 3) != 0)) return;
-    const int r = 4 * q;
-    const int cnt = len - r < 4 ? len - r : 4;
+    int b, r, cnt;
+    if (!latent_bwd_quad(len, blocks_per_object, b, r, cnt)) return;
     const size_t L = (size_t)len;
-    const size_t loc0 = 2 * (size_t)b * L, ls0 = loc0 + L, el0 = (size_t)b * L;
-    const bool al = ptr_aligned != 0;
-    const bool vec_loc = al && (loc0 & 3) == 0, vec_ls = al && (ls0 & 3) == 0;
+    const LatentRows w = latent_rows(b, len, ptr_aligned);
     float loc[4], ls[4], ga[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    quad_load(skip, loc0 + r, cnt, vec_loc, 1.0f, loc);
-    quad_load(skip, ls0 + r, cnt, vec_ls, 1.0f, ls);
+    quad_load(skip, w.loc0 + r, cnt, w.vec_loc, 1.0f, loc);
+    quad_load(skip, w.ls0 + r, cnt, w.vec_ls, 1.0f, ls);
     const float G = g_kl != nullptr ? g_kl[b] : 0.0f;
     // ONE copy of the sampler and of the float64 code, walked four times: the element is picked by selects, not by a run-time index
 #pragma unroll 1
     for (int j = 0; j < 4; ++j) {                       // (elements past len are computed on the fill and not stored)
         float da, db;
-        const float a = beta_latent_pr(j == 0 ? loc[0] : (j == 1 ? loc[1] : (j == 2 ? loc[2] : loc[3])), da);
-        const float b1 = beta_latent_pr(j == 0 ? ls[0] : (j == 1 ? ls[1] : (j == 2 ? ls[2] : ls[3])), db);
-        const unsigned long long e = rng.first_elem + el0 + r + j;
+        const float a = positive_range(j == 0 ? loc[0] : (j == 1 ? loc[1] : (j == 2 ? loc[2] : loc[3])), da);
+        const float b1 = positive_range(j == 0 ? ls[0] : (j == 1 ? ls[1] : (j == 2 ? ls[2] : ls[3])), db);
+        const unsigned long long e = rng.first + w.el0 + r + j;
         double pa = 0.0, pb = 0.0;
         if (g_z != nullptr && j < cnt) {
 #pragma unroll 1
@@ -188,25 +154,14 @@ __global__ __launch_bounds__(kBetaLatentBwdThreads) void beta_latent_bwd_kernel(
         ga[0] = j == 0 ? va : ga[0], ga[1] = j == 1 ? va : ga[1], ga[2] = j == 2 ? va : ga[2], ga[3] = j == 3 ? va : ga[3];
         gb[0] = j == 0 ? vb : gb[0], gb[1] = j == 1 ? vb : gb[1], gb[2] = j == 2 ? vb : gb[2], gb[3] = j == 3 ? vb : gb[3];
     }
-    quad_store(g_skip, loc0 + r, cnt, vec_loc, ga);
-    quad_store(g_skip, ls0 + r, cnt, vec_ls, gb);
-}
-
-static int beta_latent_check(const char *what, int B, int len, int ns, long long first_object, unsigned level)
-{
-    CTPVAE_REQUIRE(B > 0 && len > 0 && ns > 0, "%s: sizes must be positive (B=%d len=%d ns=%d)", what, B, len, ns);
-    CTPVAE_REQUIRE(ns <= kBetaLatentMaxNs, "%s: ns must be at most 2048 (got %d)", what, ns);
-    CTPVAE_REQUIRE(level <= 255u, "%s: level must be at most 255 (got %u)", what, level);
-    CTPVAE_REQUIRE((long long)ns * B <= INT_MAX && (long long)ns * B * len <= INT_MAX,
-                   "%s: ns * B * len must fit 31 bits (B=%d len=%d ns=%d)", what, B, len, ns);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / len - B,
-                   "%s: first_object must be >= 0 and (first_object + B) * len must fit 63 bits (got %lld)", what, first_object);
-    return CTPVAE_OK;
+    quad_store(g_skip, w.loc0 + r, cnt, w.vec_loc, ga);
+    quad_store(g_skip, w.ls0 + r, cnt, w.vec_ls, gb);
 }
 
 static BetaLatentRng beta_latent_rng(int len, long long first_object, unsigned long long seed, unsigned draw, unsigned level)
 {
-    return BetaLatentRng{(unsigned long long)first_object * (unsigned long long)len, draw, level, (unsigned)seed, (unsigned)(seed >> 32)};
+    const QuadRng q = quad_rng(first_object, len, seed, draw);
+    return BetaLatentRng{q.first, q.draw, level, q.k0, q.k1};
 }
 
 }  // namespace ctpvae
@@ -220,15 +175,15 @@ int ctpvae_beta_latent_fwd_f32(const float *skip_dev, int B, int len, int ns, lo
                                ctpvae_stream_t stream)
 {
     CTPVAE_REQUIRE(skip_dev && z_out_dev, "beta_latent_fwd: null pointer");
-    if (int rc = beta_latent_check("beta_latent_fwd", B, len, ns, first_object, level)) return rc;
+    if (int rc = latent_check("beta_latent_fwd", B, len, ns, kBetaLatentMaxNs, first_object, level)) return rc;
     const BetaLatentRng rng = beta_latent_rng(len, first_object, seed, draw, level);
     const int aligned = head_aligned16({skip_dev, kl_elem_out_dev}) ? 1 : 0;
-    const int chunks = (len + kBetaLatentFwdThreads - 1) / kBetaLatentFwdThreads;
+    const int chunks = (len + kObjectSumThreads - 1) / kObjectSumThreads;
     const int kl_blocks = (kl_sum_out_dev != nullptr || kl_elem_out_dev != nullptr) ? B : 0;
     // ns * B * chunks <= ns * B * len < 2^31 and B <= ns * B * len: the sum fits 32 unsigned bits and the grid's x limit (2^31 - 1) is checked
     const long long grid = (long long)kl_blocks + (long long)ns * B * chunks;
     CTPVAE_REQUIRE(grid <= INT_MAX, "beta_latent_fwd: too many workgroups (B=%d len=%d ns=%d)", B, len, ns);
-    hipLaunchKernelGGL(beta_latent_fwd_kernel, dim3((unsigned)grid), dim3(kBetaLatentFwdThreads), 0, (hipStream_t)stream, skip_dev, B, len,
+    hipLaunchKernelGGL(beta_latent_fwd_kernel, dim3((unsigned)grid), dim3(kObjectSumThreads), 0, (hipStream_t)stream, skip_dev, B, len,
                        chunks, kl_blocks, rng, aligned, z_out_dev, kl_sum_out_dev, kl_elem_out_dev, aux_out_dev);
     CTPVAE_LAUNCH_CHECK("beta_latent_fwd_kernel");
     return CTPVAE_OK;
@@ -238,12 +193,11 @@ int ctpvae_beta_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, lo
                                unsigned level, const float *g_z_dev, const float *g_kl_dev, float *g_skip_out_dev, ctpvae_stream_t stream)
 {
     CTPVAE_REQUIRE(skip_dev && g_skip_out_dev, "beta_latent_bwd: null pointer");
-    if (int rc = beta_latent_check("beta_latent_bwd", B, len, ns, first_object, level)) return rc;
+    if (int rc = latent_check("beta_latent_bwd", B, len, ns, kBetaLatentMaxNs, first_object, level)) return rc;
     const BetaLatentRng rng = beta_latent_rng(len, first_object, seed, draw, level);
     const int aligned = head_aligned16({skip_dev, g_skip_out_dev}) ? 1 : 0;
-    const int quads = (len >> 2) + ((len & 3) != 0);
-    const int bpo = (quads + kBetaLatentBwdThreads - 1) / kBetaLatentBwdThreads;     // B * bpo <= B * len < 2^31
-    hipLaunchKernelGGL(beta_latent_bwd_kernel, dim3((unsigned)B * (unsigned)bpo), dim3(kBetaLatentBwdThreads), 0, (hipStream_t)stream, skip_dev,
+    const int bpo = latent_blocks_per_object(len);
+    hipLaunchKernelGGL(beta_latent_bwd_kernel, dim3((unsigned)B * (unsigned)bpo), dim3(kQuadBwdThreads), 0, (hipStream_t)stream, skip_dev,
                        B, len, ns, rng, aligned, bpo, g_z_dev, g_kl_dev, g_skip_out_dev);
     CTPVAE_LAUNCH_CHECK("beta_latent_bwd_kernel");
     return CTPVAE_OK;
@@ -253,17 +207,16 @@ int ctpvae_beta_latent_words_host_u32(int n, int len, long long first_object, un
                                       int gamma, int attempt, unsigned *out_host)
 {
     CTPVAE_REQUIRE(out_host, "beta_latent_words_host: null pointer");
-    if (int rc = beta_latent_check("beta_latent_words_host", n, len, 1, first_object, level)) return rc;
+    if (int rc = latent_check("beta_latent_words_host", n, len, 1, kBetaLatentMaxNs, first_object, level)) return rc;
     CTPVAE_REQUIRE(s >= 0 && s < kBetaLatentMaxNs, "beta_latent_words_host: 0 <= s < 2048 (got %d)", s);
     CTPVAE_REQUIRE(gamma >= 0 && gamma <= 1 && attempt >= 0 && attempt < kBetaAttempts,
                    "beta_latent_words_host: gamma must be 0 or 1 and 0 <= attempt < 16 (got %d, %d)", gamma, attempt);
-    const unsigned long long e0 = (unsigned long long)first_object * (unsigned long long)len;
+    const BetaLatentRng rng = beta_latent_rng(len, first_object, seed, draw, level);
     const long long total = (long long)n * len;
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     const unsigned word3 = beta_latent_word3(level, (unsigned)s, (unsigned)gamma) | (unsigned)attempt;
     for (long long i = 0; i < total; ++i) {
-        const unsigned long long e = e0 + (unsigned long long)i;
-        const Philox4 blk = philox4x32_10((unsigned)e, (unsigned)(e >> 32), draw, word3, k0, k1);
+        const unsigned long long e = rng.first + (unsigned long long)i;
+        const Philox4 blk = philox4x32_10((unsigned)e, (unsigned)(e >> 32), draw, word3, rng.k0, rng.k1);
         for (int w = 0; w < 4; ++w) out_host[4 * i + w] = blk.w[w];
     }
     return CTPVAE_OK;

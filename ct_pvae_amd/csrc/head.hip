@@ -4,7 +4,7 @@
 //
 // The function, per pixel, fp32 (EPS = FLT_EPSILON, LO = 1e-7f, HI = (float)(1 - 1e-7) = 1 - 2^-23; low = 0, high = 1e10 of the
 // truncation are fixed: Phi((1e10 - loc) / scale) is exactly 1):
-//   pr(t)  = t >= 1 ? t : exp(t - 1) + EPS;   loc = pr(alpha), scale = pr(beta)
+//   pr(t)  = t >= 1 ? t : exp(t - 1) + EPS;   loc = pr(alpha), scale = pr(beta)                    (quad_io.h's positive_range)
 //   a      = -loc / scale;   Pa = Phi(a);   Z = max(1 - Pa, 1e-30)           (loc > 0: Z >= 0.5, the clamp never acts)
 //   p      = clamp(Pa + u Z, LO, HI);   z = ndtri(p);   x = max(loc + scale z, 0)
 //   zeta   = (x - loc) / scale;   lp = ((-zeta^2 / 2 - log(2 pi) / 2) - log scale) - log Z
@@ -30,16 +30,10 @@
 // u = ((w >> 8) + 0.5f) * 2^-24 in fp32 (hmc.hip's form): never 0, never 1.  u depends on (seed, draw, e) alone, so a batch cut
 // into calls (or ranks) with first_object draws what the whole batch draws.  A non-null u_in [n][pix] replaces the generator.
 //
-// Layout and the order of the per-object sum (fixed by the pixel's index INSIDE its object, so LP[o] has the same bits whatever n,
-// first_object and the object's alignment in memory are).  One workgroup of 1024 threads = 16 waves per object; no atomics.
-//   quad q of the object = its pixels 4q .. 4q+3:  s_q = ((lp_4q + lp_4q+1) + lp_4q+2) + lp_4q+3       (pixels past pix add +0.0f)
-//   thread t takes the quads t, t + 1024, t + 2048, ...:  acc_t = ((0 + s_t) + s_(t+1024)) + ...      (a thread without a quad: +0.0f)
-//   wave w = threads 64w .. 64w+63:  W_w = wave_sum(acc) -- the xor butterfly 32, 16, 8, 4, 2, 1 of loglik_math.h
-//   LP[o] = ((W_0 + W_1) + W_2) + ... + W_15                                                          (ascending, one at a time)
-// The longest chain of additions is 3 + ceil(ceil(pix / 4) / 1024) + 6 + 15.
-// A quad is moved with one 16-byte access when it is whole and 16-byte aligned in memory (object offset o * pix a multiple of 4,
-// pointers 16-byte aligned), with guarded 4-byte accesses otherwise.  The backward has no sum: it walks the n * pix pixels as
-// memory quads, 256 threads per workgroup.
+// Layout and the order of the per-object sum LP[o]: quad_io.h states them (head_fwd_body, head_bwd_body) -- one workgroup of 1024
+// threads per object, no atomics, the order fixed by the pixel's index INSIDE its object, so LP[o] has the same bits whatever n,
+// first_object and the object's alignment in memory are; the backward has no sum and walks the n * pix pixels as memory quads, 256
+// threads per workgroup.
 //
 // The pixel's function, its constants and the Philox layout live in tn_head.h, which marginals.hip shares.
 #include "tn_head.h"
@@ -47,84 +41,61 @@
 namespace ctpvae {
 
 static_assert(kHeadTag == 0x544E48u, "kHeadTag = 0x544E48u is part of the stream's definition (include/ctpvae_radon.h)");
-constexpr int kHeadFwdThreads = kObjectSumThreads;
-constexpr int kHeadBwdThreads = 256;
 
-struct HeadRng {
-    unsigned long long first_pixel;   // first_object * pix
-    unsigned draw, k0, k1;
+struct HeadRng : QuadRng {
     const float *u_in;                // [n][pix] or nullptr
 };
 
-__global__ __launch_bounds__(kHeadFwdThreads) void tn_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
-                                                                      int pix, HeadRng rng, int ptr_aligned, float *__restrict__ x_out,
-                                                                      float *__restrict__ lp_sum, float *__restrict__ lp_elem)
+// the uniforms of the quad at i: drawn once per quad, or loaded from u_in
+__device__ __forceinline__ void tn_quad_uniforms(const HeadRng &rng, size_t i, int cnt, bool vec, float (&u)[4])
 {
-    __shared__ float wsum[kHeadFwdThreads / 64];
-    const int o = blockIdx.x, t = threadIdx.x;
-    const size_t base = (size_t)o * pix;
-    const bool vec = ptr_aligned != 0 && (base & 3) == 0;
-    const int quads = (pix + 3) >> 2;
-    float acc = 0.0f;
-    for (int q = t; q < quads; q += kHeadFwdThreads) {
-        const int r = 4 * q;
-        const int cnt = pix - r < 4 ? pix - r : 4;
-        const size_t i = base + r;
-        float al[4], be[4], u[4], x[4], lp[4];
-        quad_load(alpha, i, cnt, vec, 1.0f, al);
-        quad_load(beta, i, cnt, vec, 1.0f, be);
-        if (rng.u_in != nullptr) quad_load(rng.u_in, i, cnt, vec, 0.5f, u);
-        else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const TnPixel px = tn_pixel<false>(al[j], be[j], u[j]);
-            x[j] = px.x;
-            lp[j] = j < cnt ? px.lp : 0.0f;
-        }
-        quad_store(x_out, i, cnt, vec, x);
-        if (lp_elem != nullptr) quad_store(lp_elem, i, cnt, vec, lp);
-        acc += ((lp[0] + lp[1]) + lp[2]) + lp[3];
-    }
-    const float s = object_sum_1024(acc, wsum, t);
-    if (t == 0) lp_sum[o] = s;
+    if (rng.u_in != nullptr) quad_load(rng.u_in, i, cnt, vec, 0.5f, u);
+    else head_uniforms4(rng.first + i, rng.draw, rng.k0, rng.k1, u);
 }
 
-__global__ __launch_bounds__(kHeadBwdThreads) void tn_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+__global__ __launch_bounds__(kObjectSumThreads) void tn_head_fwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
+                                                                        int pix, HeadRng rng, int ptr_aligned, float *__restrict__ x_out,
+                                                                        float *__restrict__ lp_sum, float *__restrict__ lp_elem)
+{
+    head_fwd_body(alpha, beta, pix, ptr_aligned, x_out, lp_sum, lp_elem,
+                  [&](const float (&al)[4], const float (&be)[4], size_t i, int cnt, bool vec, float (&x)[4], float (&lp)[4]) {
+                      float u[4];
+                      tn_quad_uniforms(rng, i, cnt, vec, u);
+#pragma unroll
+                      for (int j = 0; j < 4; ++j) {
+                          const TnPixel px = tn_pixel<false>(al[j], be[j], u[j]);
+                          x[j] = px.x, lp[j] = px.lp;
+                      }
+                  });
+}
+
+__device__ __forceinline__ void tn_pixel_grad(const TnPixel &px, float gx, float G, float &g_alpha, float &g_beta)
+{
+    const float rs = 1.0f / px.scale;
+    const float gzs = G * px.zeta * rs;
+    const float gx0 = px.pass_x ? gx - gzs : 0.0f;
+    const float gp = px.pass_p ? gx0 * px.scale * px.D : 0.0f;
+    const float phi = kInvSqrt2Pi * expf(-0.5f * (px.a * px.a));
+    const float gA = phi * (gp * px.omu + G / px.Z);
+    const float gloc = (gx0 + gzs) - gA * rs;
+    const float gscale = (gx0 * px.z + G * (px.zeta * px.zeta - 1.0f) * rs) - gA * px.a * rs;
+    g_alpha = gloc * px.dloc;
+    g_beta = gscale * px.dscale;
+}
+
+__global__ __launch_bounds__(kQuadBwdThreads) void tn_head_bwd_kernel(const float *__restrict__ alpha, const float *__restrict__ beta,
                                                                       long long total, int pix, HeadRng rng, int ptr_aligned,
                                                                       const float *__restrict__ g_x, const float *__restrict__ g_lp,
                                                                       float *__restrict__ g_alpha, float *__restrict__ g_beta)
 {
-    const long long i0 = 4 * ((long long)blockIdx.x * kHeadBwdThreads + threadIdx.x);
-    if (i0 >= total) return;
-    const int cnt = total - i0 < 4 ? (int)(total - i0) : 4;
-    const size_t i = (size_t)i0;
-    const bool vec = ptr_aligned != 0;
-    float al[4], be[4], u[4], gx[4], ga[4], gb[4];
-    quad_load(alpha, i, cnt, vec, 1.0f, al);
-    quad_load(beta, i, cnt, vec, 1.0f, be);
-    if (rng.u_in != nullptr) quad_load(rng.u_in, i, cnt, vec, 0.5f, u);
-    else head_uniforms4(rng.first_pixel + i, rng.draw, rng.k0, rng.k1, u);
-    if (g_x != nullptr) quad_load(g_x, i, cnt, vec, 0.0f, gx);
-    else gx[0] = gx[1] = gx[2] = gx[3] = 0.0f;
+    head_bwd_body(alpha, beta, total, pix, ptr_aligned, g_x, g_lp, g_alpha, g_beta,
+                  [&](const float (&al)[4], const float (&be)[4], size_t i, int cnt, bool vec, const float (&gx)[4], const float (&G)[4],
+                      float (&ga)[4], float (&gb)[4]) {
+                      float u[4];
+                      tn_quad_uniforms(rng, i, cnt, vec, u);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        // the pixel's object: total < 2^31, so 32-bit division (pixels past the end read object n - 1)
-        const unsigned e = (unsigned)(j < cnt ? i0 + j : i0);
-        const float G = g_lp != nullptr ? g_lp[e / (unsigned)pix] : 0.0f;
-        const TnPixel px = tn_pixel<true>(al[j], be[j], u[j]);
-        const float rs = 1.0f / px.scale;
-        const float gzs = G * px.zeta * rs;
-        const float gx0 = px.pass_x ? gx[j] - gzs : 0.0f;
-        const float gp = px.pass_p ? gx0 * px.scale * px.D : 0.0f;
-        const float phi = kInvSqrt2Pi * expf(-0.5f * (px.a * px.a));
-        const float gA = phi * (gp * px.omu + G / px.Z);
-        const float gloc = (gx0 + gzs) - gA * rs;
-        const float gscale = (gx0 * px.z + G * (px.zeta * px.zeta - 1.0f) * rs) - gA * px.a * rs;
-        ga[j] = gloc * px.dloc;
-        gb[j] = gscale * px.dscale;
-    }
-    quad_store(g_alpha, i, cnt, vec, ga);
-    quad_store(g_beta, i, cnt, vec, gb);
+                      for (int j = 0; j < 4; ++j) tn_pixel_grad(tn_pixel<true>(al[j], be[j], u[j]), gx[j], G[j], ga[j], gb[j]);
+                  });
 }
 
 }  // namespace ctpvae
@@ -139,9 +110,9 @@ int ctpvae_tn_head_fwd_f32(const float *alpha_dev, const float *beta_dev, int n,
 {
     if (int rc = head_check("tn_head_fwd", alpha_dev, beta_dev, n, pix, first_object)) return rc;
     CTPVAE_REQUIRE(x_out_dev && lp_sum_out_dev, "tn_head_fwd: null output pointer");
-    const HeadRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32), u_dev};
+    const HeadRng rng{quad_rng(first_object, pix, seed, draw), u_dev};
     const int aligned = head_aligned16({alpha_dev, beta_dev, u_dev, x_out_dev, lp_elem_out_dev}) ? 1 : 0;
-    hipLaunchKernelGGL(tn_head_fwd_kernel, dim3(n), dim3(kHeadFwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, pix, rng, aligned,
+    hipLaunchKernelGGL(tn_head_fwd_kernel, dim3(n), dim3(kObjectSumThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, pix, rng, aligned,
                        x_out_dev, lp_sum_out_dev, lp_elem_out_dev);
     CTPVAE_LAUNCH_CHECK("tn_head_fwd_kernel");
     return CTPVAE_OK;
@@ -153,12 +124,10 @@ int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n,
 {
     if (int rc = head_check("tn_head_bwd", alpha_dev, beta_dev, n, pix, first_object)) return rc;
     CTPVAE_REQUIRE(g_alpha_out_dev && g_beta_out_dev, "tn_head_bwd: null output pointer");
-    const HeadRng rng{(unsigned long long)first_object * (unsigned long long)pix, draw, (unsigned)seed, (unsigned)(seed >> 32), u_dev};
+    const HeadRng rng{quad_rng(first_object, pix, seed, draw), u_dev};
     const int aligned = head_aligned16({alpha_dev, beta_dev, u_dev, g_x_dev, g_alpha_out_dev, g_beta_out_dev}) ? 1 : 0;
     const long long total = (long long)n * pix;
-    const long long per_block = 4ll * kHeadBwdThreads;
-    const unsigned grid = (unsigned)((total + per_block - 1) / per_block);
-    hipLaunchKernelGGL(tn_head_bwd_kernel, dim3(grid), dim3(kHeadBwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, total, pix, rng,
+    hipLaunchKernelGGL(tn_head_bwd_kernel, dim3(head_bwd_grid(total)), dim3(kQuadBwdThreads), 0, (hipStream_t)stream, alpha_dev, beta_dev, total, pix, rng,
                        aligned, g_x_dev, g_lp_dev, g_alpha_out_dev, g_beta_out_dev);
     CTPVAE_LAUNCH_CHECK("tn_head_bwd_kernel");
     return CTPVAE_OK;
@@ -167,16 +136,12 @@ int ctpvae_tn_head_bwd_f32(const float *alpha_dev, const float *beta_dev, int n,
 int ctpvae_tn_head_uniforms_host_f32(int n, int pix, long long first_object, unsigned long long seed, unsigned draw, float *u_out_host)
 {
     CTPVAE_REQUIRE(u_out_host, "tn_head_uniforms_host: null pointer");
-    CTPVAE_REQUIRE(n > 0 && pix > 0, "tn_head_uniforms_host: sizes must be positive (n=%d pix=%d)", n, pix);
-    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "tn_head_uniforms_host: n * pix must fit 31 bits (n=%d pix=%d)", n, pix);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
-                   "tn_head_uniforms_host: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", first_object);
-    const unsigned long long e0 = (unsigned long long)first_object * (unsigned long long)pix;
+    if (int rc = head_size_check("tn_head_uniforms_host", n, pix, first_object)) return rc;
+    const QuadRng rng = quad_rng(first_object, pix, seed, draw);
     const long long total = (long long)n * pix;
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     for (long long i = 0; i < total; ++i) {
-        const unsigned long long e = e0 + (unsigned long long)i;
-        u_out_host[i] = head_u24(philox_word(head_block(e >> 2, draw, k0, k1), (unsigned)e & 3u));
+        const unsigned long long e = rng.first + (unsigned long long)i;
+        u_out_host[i] = head_u24(philox_word(head_block(e >> 2, draw, rng.k0, rng.k1), (unsigned)e & 3u));
     }
     return CTPVAE_OK;
 }

@@ -6,7 +6,7 @@
 // Input: skip [B][2C][H][W], contiguous, the encoder's output at the level.  Channels 0 .. C-1 are loc, C .. 2C-1 are log_scale: with
 // len = C H W, object b's loc is at b * 2 len and its log_scale at b * 2 len + len.  Per element i of object b and sample s, fp32
 // (EPS = FLT_EPSILON):
-//   pr(t)   = t >= 1 ? t : exp(t - 1) + EPS                         (head.hip's positive_range)
+//   pr(t)   = t >= 1 ? t : exp(t - 1) + EPS                         (quad_io.h's positive_range)
 //   scale   = pr(log_scale) + sqrt_reg
 //   z[s * B + b][i] = loc + scale * eps(s, b, i)                    (sample-major: the layout the decoder is fed)
 //   kl[b][i] = 0.5f * (scale * scale + loc * loc - 1.0f) - logf(scale)     (trainer.kl_normal_std, the same association)
@@ -27,28 +27,16 @@
 // relative, and no clamp is needed.  eps depends on (seed, draw, level, s, global object, i) alone, so a batch cut over calls or ranks
 // with first_object draws what the whole batch draws, for any ns.  A non-null eps_in [ns * B][len] replaces the generator (tests).
 //
-// Layout and the order of the per-object sum: head.hip's.  One workgroup of 1024 threads = 16 waves per object; no atomics.
-//   quad q of the object = its elements 4q .. 4q+3:  s_q = ((kl_4q + kl_4q+1) + kl_4q+2) + kl_4q+3     (elements past len add +0.0f)
-//   thread t takes the quads t, t + 1024, ...:  acc_t = ((0 + s_t) + s_(t+1024)) + ...                 (a thread without a quad: +0.0f)
-//   KL[b] = ((W_0 + W_1) + W_2) + ... + W_15,  W_w = wave_sum(acc) of wave w                           (quad_io.h: object_sum_1024)
-// so KL[b] has the same bits whatever B, first_object and the object's alignment in memory are.  A quad of an array is moved with one
-// 16-byte access when it is whole and 16-byte aligned in memory (the pointers 16-byte aligned and the row's offset -- 2 b len,
-// 2 b len + len, (s B + b) len, b len -- a multiple of 4), with guarded 4-byte accesses otherwise.  The backward has no sum: 256
-// threads per workgroup, ceil(quads / 256) workgroups per object.
-#include <climits>
-#include <initializer_list>
-
-#include "common.h"
-#include "loglik_math.h"
-#include "philox.h"
+// Layout and the order of the per-object sum KL[b]: quad_io.h states them (latent_kl_walk, whose pass over a quad also draws and
+// stores the quad's ns samples), so KL[b] has the same bits whatever B, first_object and the object's alignment in memory are.  The
+// row offsets whose multiple of 4 decides a quad's 16-byte access are 2 b len, 2 b len + len, (s B + b) len and b len.  The backward
+// has no sum: 256 threads per workgroup, ceil(quads / 256) workgroups per object.
 #include "quad_io.h"
 
 namespace ctpvae {
 
 constexpr unsigned kLatentTag = 0x4C000000u;   // 'L' in the top byte of the fourth counter word; level in bits 16 .. 23, s below
-constexpr int kLatentFwdThreads = kObjectSumThreads;
-constexpr int kLatentBwdThreads = 256;
-constexpr float kLatentEps = 1.1920928955078125e-07f;    // FLT_EPSILON, positive_range's offset
+constexpr int kLatentMaxNs = 65535;
 
 // the tail probability of a word: ((w >> 7) & 0xFFFFFF) + 0.5 in units of 2^-25; bit 31 is the sign of the draw
 __host__ __device__ inline float latent_tail(unsigned w) { return ((float)((w >> 7) & 0xFFFFFFu) + 0.5f) * 2.98023223876953125e-08f; }
@@ -64,9 +52,8 @@ __device__ __forceinline__ float latent_eps(unsigned w)
     return (w >> 31) != 0 ? q : -q;
 }
 
-struct LatentRng {
-    unsigned long long first_elem;   // first_object * len
-    unsigned draw, tag, k0, k1;      // tag = kLatentTag | level << 16
+struct LatentRng : QuadRng {
+    unsigned tag;                    // kLatentTag | level << 16
     const float *eps_in;             // [ns * B][len] or nullptr
 };
 
@@ -81,75 +68,60 @@ __device__ __forceinline__ void latent_eps4(unsigned long long e, const LatentRn
     for (unsigned j = 0; j < 4; ++j) eps[j] = latent_eps(sh + j < 4 ? philox_word(A, sh + j) : philox_word(B, sh + j - 4));
 }
 
-__global__ __launch_bounds__(kLatentFwdThreads) void latent_fwd_kernel(const float *__restrict__ skip, int B, int len, int ns, float sqrt_reg,
-                                                                        LatentRng rng, int ptr_aligned, float *__restrict__ z_out,
-                                                                        float *__restrict__ kl_sum, float *__restrict__ kl_elem,
-                                                                        float *__restrict__ eps_out)
+// the draws of sample s for the quad at r of object b (its row of a [ns * B][len] array starts at `row`): drawn, or loaded from eps_in
+__device__ __forceinline__ void latent_quad_eps(const LatentRng &rng, const LatentRows &w, size_t row, int r, int cnt, bool vec_z, int s,
+                                                float (&eps)[4])
 {
-    __shared__ float wsum[kLatentFwdThreads / 64];
-    const int b = blockIdx.x, t = threadIdx.x;
-    const size_t L = (size_t)len;
-    const size_t loc0 = 2 * (size_t)b * L, ls0 = loc0 + L, el0 = (size_t)b * L;
-    const bool al = ptr_aligned != 0;
-    const bool vec_loc = al && (loc0 & 3) == 0, vec_ls = al && (ls0 & 3) == 0, vec_el = al && (el0 & 3) == 0;
-    const int quads = (len >> 2) + ((len & 3) != 0);
-    float acc = 0.0f;
-    for (int q = t; q < quads; q += kLatentFwdThreads) {
-        const int r = 4 * q;
-        const int cnt = len - r < 4 ? len - r : 4;
-        float loc[4], ls[4], scale[4], kl[4];
-        quad_load(skip, loc0 + r, cnt, vec_loc, 0.0f, loc);
-        quad_load(skip, ls0 + r, cnt, vec_ls, 1.0f, ls);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            scale[j] = (ls[j] >= 1.0f ? ls[j] : expf(ls[j] - 1.0f) + kLatentEps) + sqrt_reg;
-            const float v = 0.5f * (scale[j] * scale[j] + loc[j] * loc[j] - 1.0f) - logf(scale[j]);
-            kl[j] = j < cnt ? v : 0.0f;
-        }
-        if (kl_elem != nullptr) quad_store(kl_elem, el0 + r, cnt, vec_el, kl);
-        acc += ((kl[0] + kl[1]) + kl[2]) + kl[3];
-        for (int s = 0; s < ns; ++s) {
-            const size_t row = ((size_t)s * B + b) * L;
-            const bool vec_z = al && (row & 3) == 0;
-            float eps[4], z[4];
-            if (rng.eps_in != nullptr) quad_load(rng.eps_in, row + r, cnt, vec_z, 0.0f, eps);
-            else latent_eps4(rng.first_elem + el0 + r, rng, (unsigned)s, eps);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = loc[j] + scale[j] * eps[j];
-            quad_store(z_out, row + r, cnt, vec_z, z);
-            if (eps_out != nullptr) quad_store(eps_out, row + r, cnt, vec_z, eps);
-        }
-    }
-    const float total = object_sum_1024(acc, wsum, t);
-    if (t == 0) kl_sum[b] = total;
+    if (rng.eps_in != nullptr) quad_load(rng.eps_in, row + r, cnt, vec_z, 0.0f, eps);
+    else latent_eps4(rng.first + w.el0 + r, rng, (unsigned)s, eps);
 }
 
-__global__ __launch_bounds__(kLatentBwdThreads) void latent_bwd_kernel(const float *__restrict__ skip, int B, int len, int ns, float sqrt_reg,
-                                                                        LatentRng rng, int ptr_aligned, int blocks_per_object,
-                                                                        const float *__restrict__ g_z, const float *__restrict__ g_kl,
-                                                                        float *__restrict__ g_skip)
+__global__ __launch_bounds__(kObjectSumThreads) void latent_fwd_kernel(const float *__restrict__ skip, int B, int len, int ns, float sqrt_reg,
+                                                                       LatentRng rng, int ptr_aligned, float *__restrict__ z_out,
+                                                                       float *__restrict__ kl_sum, float *__restrict__ kl_elem,
+                                                                       float *__restrict__ eps_out)
 {
-    const int b = blockIdx.x / blocks_per_object;
-    const int q = (blockIdx.x - b * blocks_per_object) * kLatentBwdThreads + threadIdx.x;
-    if (q >= (len >> 2) + ((len & 3) != 0)) return;
-    const int r = 4 * q;
-    const int cnt = len - r < 4 ? len - r : 4;
-    const size_t L = (size_t)len;
-    const size_t loc0 = 2 * (size_t)b * L, ls0 = loc0 + L, el0 = (size_t)b * L;
-    const bool al = ptr_aligned != 0;
-    const bool vec_loc = al && (loc0 & 3) == 0, vec_ls = al && (ls0 & 3) == 0;
+    const int b = blockIdx.x;
+    latent_kl_walk(skip, b, len, ptr_aligned, 0.0f, kl_sum, kl_elem,
+                   [&](const LatentRows &w, int r, int cnt, const float (&loc)[4], const float (&ls)[4], float (&kl)[4]) {
+                       float scale[4], unused;
+#pragma unroll
+                       for (int j = 0; j < 4; ++j) {
+                           scale[j] = positive_range(ls[j], unused) + sqrt_reg;
+                           kl[j] = 0.5f * (scale[j] * scale[j] + loc[j] * loc[j] - 1.0f) - logf(scale[j]);
+                       }
+                       for (int s = 0; s < ns; ++s) {        // the quad's samples, in the same pass
+                           const size_t row = ((size_t)s * B + b) * (size_t)len;
+                           const bool vec_z = w.al && (row & 3) == 0;
+                           float eps[4], z[4];
+                           latent_quad_eps(rng, w, row, r, cnt, vec_z, s, eps);
+#pragma unroll
+                           for (int j = 0; j < 4; ++j) z[j] = loc[j] + scale[j] * eps[j];
+                           quad_store(z_out, row + r, cnt, vec_z, z);
+                           if (eps_out != nullptr) quad_store(eps_out, row + r, cnt, vec_z, eps);
+                       }
+                   });
+}
+
+__global__ __launch_bounds__(kQuadBwdThreads) void latent_bwd_kernel(const float *__restrict__ skip, int B, int len, int ns, float sqrt_reg,
+                                                                     LatentRng rng, int ptr_aligned, int blocks_per_object,
+                                                                     const float *__restrict__ g_z, const float *__restrict__ g_kl,
+                                                                     float *__restrict__ g_skip)
+{
+    int b, r, cnt;
+    if (!latent_bwd_quad(len, blocks_per_object, b, r, cnt)) return;
+    const LatentRows w = latent_rows(b, len, ptr_aligned);
     float loc[4], ls[4], gloc[4], gscale[4];
-    quad_load(skip, loc0 + r, cnt, vec_loc, 0.0f, loc);
-    quad_load(skip, ls0 + r, cnt, vec_ls, 1.0f, ls);
+    quad_load(skip, w.loc0 + r, cnt, w.vec_loc, 0.0f, loc);
+    quad_load(skip, w.ls0 + r, cnt, w.vec_ls, 1.0f, ls);
     gloc[0] = gloc[1] = gloc[2] = gloc[3] = 0.0f;
     gscale[0] = gscale[1] = gscale[2] = gscale[3] = 0.0f;
     if (g_z != nullptr)
         for (int s = 0; s < ns; ++s) {
-            const size_t row = ((size_t)s * B + b) * L;
-            const bool vec_z = al && (row & 3) == 0;
+            const size_t row = ((size_t)s * B + b) * (size_t)len;
+            const bool vec_z = w.al && (row & 3) == 0;
             float eps[4], gz[4];
-            if (rng.eps_in != nullptr) quad_load(rng.eps_in, row + r, cnt, vec_z, 0.0f, eps);
-            else latent_eps4(rng.first_elem + el0 + r, rng, (unsigned)s, eps);
+            latent_quad_eps(rng, w, row, r, cnt, vec_z, s, eps);
             quad_load(g_z, row + r, cnt, vec_z, 0.0f, gz);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -160,39 +132,18 @@ __global__ __launch_bounds__(kLatentBwdThreads) void latent_bwd_kernel(const flo
     const float G = g_kl != nullptr ? g_kl[b] : 0.0f;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        const float e = expf(ls[j] - 1.0f);
-        const float scale = (ls[j] >= 1.0f ? ls[j] : e + kLatentEps) + sqrt_reg;
-        const float dscale = ls[j] >= 1.0f ? 1.0f : e;
+        float dscale;
+        const float scale = positive_range(ls[j], dscale) + sqrt_reg;
         gloc[j] = gloc[j] + G * loc[j];
         gscale[j] = (gscale[j] + G * (scale - 1.0f / scale)) * dscale;
     }
-    quad_store(g_skip, loc0 + r, cnt, vec_loc, gloc);
-    quad_store(g_skip, ls0 + r, cnt, vec_ls, gscale);
-}
-
-static int latent_check(const char *what, int B, int len, int ns, long long first_object, unsigned level)
-{
-    CTPVAE_REQUIRE(B > 0 && len > 0 && ns > 0, "%s: sizes must be positive (B=%d len=%d ns=%d)", what, B, len, ns);
-    CTPVAE_REQUIRE(ns <= 65535, "%s: ns must be at most 65535 (got %d)", what, ns);
-    CTPVAE_REQUIRE(level <= 255u, "%s: level must be at most 255 (got %u)", what, level);
-    CTPVAE_REQUIRE((long long)ns * B <= INT_MAX && (long long)ns * B * len <= INT_MAX,
-                   "%s: ns * B * len must fit 31 bits (B=%d len=%d ns=%d)", what, B, len, ns);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / len - B,
-                   "%s: first_object must be >= 0 and (first_object + B) * len must fit 63 bits (got %lld)", what, first_object);
-    return CTPVAE_OK;
-}
-
-static bool latent_aligned16(std::initializer_list<const void *> ptrs)
-{
-    for (const void *p : ptrs)
-        if (((size_t)p & 15) != 0) return false;   // (a null pointer counts as aligned)
-    return true;
+    quad_store(g_skip, w.loc0 + r, cnt, w.vec_loc, gloc);
+    quad_store(g_skip, w.ls0 + r, cnt, w.vec_ls, gscale);
 }
 
 static LatentRng latent_rng(int len, long long first_object, unsigned long long seed, unsigned draw, unsigned level, const float *eps_in)
 {
-    return LatentRng{(unsigned long long)first_object * (unsigned long long)len, draw, kLatentTag | (level << 16), (unsigned)seed,
-                     (unsigned)(seed >> 32), eps_in};
+    return LatentRng{quad_rng(first_object, len, seed, draw), kLatentTag | (level << 16), eps_in};
 }
 
 }  // namespace ctpvae
@@ -206,10 +157,10 @@ int ctpvae_latent_fwd_f32(const float *skip_dev, int B, int len, int ns, float s
                           float *kl_elem_out_dev, float *eps_out_dev, ctpvae_stream_t stream)
 {
     CTPVAE_REQUIRE(skip_dev && z_out_dev && kl_sum_out_dev, "latent_fwd: null pointer");
-    if (int rc = latent_check("latent_fwd", B, len, ns, first_object, level)) return rc;
+    if (int rc = latent_check("latent_fwd", B, len, ns, kLatentMaxNs, first_object, level)) return rc;
     const LatentRng rng = latent_rng(len, first_object, seed, draw, level, eps_dev);
-    const int aligned = latent_aligned16({skip_dev, eps_dev, z_out_dev, kl_elem_out_dev, eps_out_dev}) ? 1 : 0;
-    hipLaunchKernelGGL(latent_fwd_kernel, dim3(B), dim3(kLatentFwdThreads), 0, (hipStream_t)stream, skip_dev, B, len, ns, sqrt_reg, rng, aligned,
+    const int aligned = head_aligned16({skip_dev, eps_dev, z_out_dev, kl_elem_out_dev, eps_out_dev}) ? 1 : 0;
+    hipLaunchKernelGGL(latent_fwd_kernel, dim3(B), dim3(kObjectSumThreads), 0, (hipStream_t)stream, skip_dev, B, len, ns, sqrt_reg, rng, aligned,
                        z_out_dev, kl_sum_out_dev, kl_elem_out_dev, eps_out_dev);
     CTPVAE_LAUNCH_CHECK("latent_fwd_kernel");
     return CTPVAE_OK;
@@ -220,12 +171,11 @@ int ctpvae_latent_bwd_f32(const float *skip_dev, int B, int len, int ns, float s
                           float *g_skip_out_dev, ctpvae_stream_t stream)
 {
     CTPVAE_REQUIRE(skip_dev && g_skip_out_dev, "latent_bwd: null pointer");
-    if (int rc = latent_check("latent_bwd", B, len, ns, first_object, level)) return rc;
+    if (int rc = latent_check("latent_bwd", B, len, ns, kLatentMaxNs, first_object, level)) return rc;
     const LatentRng rng = latent_rng(len, first_object, seed, draw, level, eps_dev);
-    const int aligned = latent_aligned16({skip_dev, eps_dev, g_z_dev, g_skip_out_dev}) ? 1 : 0;
-    const int quads = (len >> 2) + ((len & 3) != 0);
-    const int bpo = (quads + kLatentBwdThreads - 1) / kLatentBwdThreads;     // B * bpo <= B * len < 2^31
-    hipLaunchKernelGGL(latent_bwd_kernel, dim3((unsigned)B * (unsigned)bpo), dim3(kLatentBwdThreads), 0, (hipStream_t)stream, skip_dev, B, len,
+    const int aligned = head_aligned16({skip_dev, eps_dev, g_z_dev, g_skip_out_dev}) ? 1 : 0;
+    const int bpo = latent_blocks_per_object(len);
+    hipLaunchKernelGGL(latent_bwd_kernel, dim3((unsigned)B * (unsigned)bpo), dim3(kQuadBwdThreads), 0, (hipStream_t)stream, skip_dev, B, len,
                        ns, sqrt_reg, rng, aligned, bpo, g_z_dev, g_kl_dev, g_skip_out_dev);
     CTPVAE_LAUNCH_CHECK("latent_bwd_kernel");
     return CTPVAE_OK;
@@ -235,14 +185,13 @@ int ctpvae_latent_draws_host_f32(int n, int len, int ns, long long first_object,
                                  float *v_out_host)
 {
     CTPVAE_REQUIRE(v_out_host, "latent_draws_host: null pointer");
-    if (int rc = latent_check("latent_draws_host", n, len, ns, first_object, level)) return rc;
-    const unsigned long long e0 = (unsigned long long)first_object * (unsigned long long)len;
+    if (int rc = latent_check("latent_draws_host", n, len, ns, kLatentMaxNs, first_object, level)) return rc;
+    const LatentRng rng = latent_rng(len, first_object, seed, draw, level, nullptr);
     const long long per_sample = (long long)n * len;
-    const unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
     for (int s = 0; s < ns; ++s)
         for (long long i = 0; i < per_sample; ++i) {
-            const unsigned long long e = e0 + (unsigned long long)i;
-            const unsigned w = philox_word(latent_block(e >> 2, draw, kLatentTag | (level << 16) | (unsigned)s, k0, k1), (unsigned)e & 3u);
+            const unsigned long long e = rng.first + (unsigned long long)i;
+            const unsigned w = philox_word(latent_block(e >> 2, draw, rng.tag | (unsigned)s, rng.k0, rng.k1), (unsigned)e & 3u);
             const float t = latent_tail(w);
             v_out_host[(long long)s * per_sample + i] = (w >> 31) != 0 ? -t : t;
         }

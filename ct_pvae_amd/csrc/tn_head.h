@@ -3,18 +3,11 @@
 // (tn_prep) and the part that does (tn_draw).  head.hip's header states the function; both files evaluate it through this code alone,
 // so one (alpha, beta, u) gives one x wherever it is computed (-ffp-contract=off: the same fp32 operations, the same bits).
 #pragma once
-#include <climits>
-#include <initializer_list>
-
-#include "common.h"
-#include "loglik_math.h"
-#include "philox.h"
 #include "quad_io.h"
 
 namespace ctpvae {
 
 constexpr unsigned kHeadTag = 0x544E48u;     // "TNH": the fourth counter word (hmc.hip: 0x484D43, poisson.hip: 0)
-constexpr float kHeadEps = 1.1920928955078125e-07f;    // FLT_EPSILON, positive_range's offset
 constexpr float kHeadPLo = 1e-7f;
 constexpr float kHeadQLo = 1.1920928955078125e-07f;    // 1 - HI, HI = (float)(1 - 1e-7) = 1 - 2^-23
 constexpr float kInvSqrt2 = 0.70710678118654752440f;
@@ -47,11 +40,8 @@ struct TnPrep {
 __device__ __forceinline__ TnPrep tn_prep(float alpha, float beta)
 {
     TnPrep r;
-    const float ea = expf(alpha - 1.0f), eb = expf(beta - 1.0f);
-    r.loc = alpha >= 1.0f ? alpha : ea + kHeadEps;
-    r.scale = beta >= 1.0f ? beta : eb + kHeadEps;
-    r.dloc = alpha >= 1.0f ? 1.0f : ea;
-    r.dscale = beta >= 1.0f ? 1.0f : eb;
+    r.loc = positive_range(alpha, r.dloc);
+    r.scale = positive_range(beta, r.dscale);
     r.a = -r.loc / r.scale;
     const float t = r.a * kInvSqrt2;
     r.Pa = 0.5f * erfcf(-t);
@@ -101,23 +91,6 @@ __device__ __forceinline__ TnPixel tn_pixel(float alpha, float beta, float u)
     if constexpr (BWD) r.D = kSqrt2Pi * expf(0.5f * (r.z * r.z));
     else r.D = 0.0f;
     return r;
-}
-
-inline int head_check(const char *what, const void *alpha, const void *beta, int n, int pix, long long first_object)
-{
-    CTPVAE_REQUIRE(alpha && beta, "%s: null pointer", what);
-    CTPVAE_REQUIRE(n > 0 && pix > 0, "%s: sizes must be positive (n=%d pix=%d)", what, n, pix);
-    CTPVAE_REQUIRE((long long)n * pix <= INT_MAX, "%s: n * pix must fit 31 bits (n=%d pix=%d)", what, n, pix);
-    CTPVAE_REQUIRE(first_object >= 0 && first_object <= LLONG_MAX / pix - n,
-                   "%s: first_object must be >= 0 and (first_object + n) * pix must fit 63 bits (got %lld)", what, first_object);
-    return CTPVAE_OK;
-}
-
-inline bool head_aligned16(std::initializer_list<const void *> ptrs)
-{
-    for (const void *p : ptrs)
-        if (((size_t)p & 15) != 0) return false;   // (a null pointer counts as aligned)
-    return true;
 }
 
 }  // namespace ctpvae

@@ -22,9 +22,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._args import check_float32
+from ._args import check_float32, counter_args
 from .forward_functions import _stream_ptr
-from .output_head import _counter_args
 
 __all__ = ["PixelMarginals", "bin_samples", "bin_columns", "hist_distance", "MAX_BINS"]
 
@@ -118,7 +117,7 @@ class PixelMarginals:
         draws = int(draws)
         if draws < 1:
             raise ValueError(f"PixelMarginals.add: draws must be >= 1 (got {draws})")
-        seed, draw0, first_object = _counter_args(seed, draw0, first_object)
+        seed, draw0, first_object = counter_args(seed, draw0, first_object)
         if draw0 + draws > 2 ** 32:
             raise ValueError(f"PixelMarginals.add: draw0 + draws must be <= 2^32, the draw is one 32-bit counter word (got {draw0} + {draws})")
         n, pix = alpha.shape[0], self.shape[0] * self.shape[1]

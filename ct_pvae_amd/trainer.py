@@ -44,12 +44,11 @@ from .forward_functions import num_proj_pix
 from .helper_functions import calculate_log_prob_M_given_R, create_sinograms
 from .latents import normal_latents
 from .marginals import PixelMarginals
+from ._sampling_common import EPS32
 from .beta_head import beta_head
 from .beta_latents import beta_latents
 from .output_head import truncated_normal_head
 from .update import FusedUpdate
-
-EPS32 = float(np.finfo(np.float32).eps)
 
 
 # ---------------------------------------------------------------------------------------------------------

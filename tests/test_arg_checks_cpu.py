@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import ct_pvae_amd as cp
+from ct_pvae_amd._lib import RadonLibraryError
 
 LIST = [1.0]
 F64_4 = torch.zeros(2, 2, 3, 4, dtype=torch.float64)
@@ -149,6 +150,94 @@ CASES = [
     (lambda: _marginals(beta=LIST), TypeError, "PixelMarginals.add: beta must be a torch tensor (got list)"),
     (lambda: _marginals(beta=torch.zeros(2, 1, 3, 4)), ValueError,
      "PixelMarginals.add: beta must be [n][1][4][3], the decoder's layout (got (2, 1, 3, 4))"),
+]
+
+# ---- what the four sampling operators check after their tensors, still before any device: the counter words (through every module that
+# takes them), the sample count and the level, the pair's shapes, the channel count, sqrt_reg, the size limits (on meta tensors: no
+# memory), the test operands, and last the refusal of a CPU tensor
+DRAW = "draw is one 32-bit counter word: 0 <= draw < 2^32"
+FIRST = "first_object must be >= 0 (got -1)"
+NS_N = "ns shares a counter word with the level: 1 <= ns <= 65535"
+NS_B = "the sample index shares a counter word with the level, the gamma and the attempt: 1 <= ns <= 2048"
+LEVEL = "level is one byte of a counter word: 0 <= level <= 255 (got 256)"
+HEAD_3 = torch.zeros(3, 1, 4, 3)
+SKIP = torch.zeros(2, 2, 3, 4)                                  # a good [B][2C][H][W]
+SKIP_ODD = torch.zeros(2, 3, 3, 4)
+HEAD_HUGE = torch.empty((2 ** 31, 1, 1, 1), device="meta")
+SKIP_HUGE = torch.empty((2, 2, 2 ** 15, 2 ** 14), device="meta")
+LKEY = dict(ns=1, level=0, **KEY)
+
+
+def _marginals_key(**key):
+    return cp.PixelMarginals((4, 3), device="cpu").add(HEAD, HEAD, draws=1, **key)
+
+
+CASES += [
+    # the counter words
+    (lambda: cp.head_uniforms(1, 1, seed=1, draw=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.head_uniforms(1, 1, seed=1, draw=2 ** 32), ValueError, DRAW + " (got 4294967296)"),
+    (lambda: cp.head_uniforms(1, 1, seed=1, draw=0, first_object=-1), ValueError, FIRST),
+    (lambda: cp.truncated_normal_head(HEAD, HEAD, seed=1, draw=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.truncated_normal_head(HEAD, HEAD, first_object=-1, **KEY), ValueError, FIRST),
+    (lambda: cp.beta_head(HEAD, HEAD, seed=1, draw=2 ** 32), ValueError, DRAW + " (got 4294967296)"),
+    (lambda: cp.beta_head(HEAD, HEAD, first_object=-1, **KEY), ValueError, FIRST),
+    (lambda: cp.beta_head_words(1, 1, seed=1, draw=-1, gamma=0, attempt=0), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.beta_head_words(1, 1, first_object=-1, gamma=0, attempt=0, **KEY), ValueError, FIRST),
+    (lambda: cp.normal_latents(SKIP, ns=1, level=0, seed=1, draw=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.normal_latents(SKIP, first_object=-1, **LKEY), ValueError, FIRST),
+    (lambda: cp.latent_draws(1, 1, ns=1, level=0, seed=1, draw=2 ** 32), ValueError, DRAW + " (got 4294967296)"),
+    (lambda: cp.latent_draws(1, 1, first_object=-1, **LKEY), ValueError, FIRST),
+    (lambda: cp.beta_latents(SKIP, ns=1, level=0, seed=1, draw=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.beta_latents(SKIP, first_object=-1, **LKEY), ValueError, FIRST),
+    (lambda: cp.beta_latent_words(1, 1, level=0, s=0, gamma=0, attempt=0, seed=1, draw=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: cp.beta_latent_words(1, 1, level=0, s=0, gamma=0, attempt=0, first_object=-1, **KEY), ValueError, FIRST),
+    (lambda: _marginals_key(seed=1, draw0=-1), ValueError, DRAW + " (got -1)"),
+    (lambda: _marginals_key(seed=1, first_object=-1), ValueError, FIRST),
+    (lambda: cp.dropout(X, 0.5, layer=0, seed=1, draw=2 ** 32), ValueError, DRAW + " (got 4294967296)"),
+    (lambda: cp.dropout(X, 0.5, layer=0, first_object=-1, **KEY), ValueError, FIRST),
+    # the sample count and the level
+    (lambda: cp.normal_latents(SKIP, ns=0, level=0, **KEY), ValueError, NS_N + " (got 0)"),
+    (lambda: cp.normal_latents(SKIP, ns=65536, level=0, **KEY), ValueError, NS_N + " (got 65536)"),
+    (lambda: cp.normal_latents(SKIP, ns=1, level=256, **KEY), ValueError, LEVEL),
+    (lambda: cp.latent_draws(1, 1, ns=0, level=0, **KEY), ValueError, NS_N + " (got 0)"),
+    (lambda: cp.latent_draws(1, 1, ns=65536, level=0, **KEY), ValueError, NS_N + " (got 65536)"),
+    (lambda: cp.latent_draws(1, 1, ns=1, level=256, **KEY), ValueError, LEVEL),
+    (lambda: cp.beta_latents(SKIP, ns=0, level=0, **KEY), ValueError, NS_B + " (got 0)"),
+    (lambda: cp.beta_latents(SKIP, ns=2049, level=0, **KEY), ValueError, NS_B + " (got 2049)"),
+    (lambda: cp.beta_latents(SKIP, ns=1, level=256, **KEY), ValueError, LEVEL),
+    (lambda: cp.beta_latent_words(1, 1, level=256, s=0, gamma=0, attempt=0, **KEY), ValueError, LEVEL),
+    (lambda: cp.beta_latent_words(1, 1, level=0, s=2048, gamma=0, attempt=0, **KEY), ValueError, "beta_latent_words: 0 <= s < 2048 (got 2048)"),
+    # the pair's shapes, the channel count, sqrt_reg
+    (lambda: cp.truncated_normal_head(HEAD, HEAD_3, **KEY), ValueError,
+     "truncated_normal_head: alpha and beta must have one shape (got (2, 1, 4, 3), (3, 1, 4, 3))"),
+    (lambda: cp.beta_head(HEAD, HEAD_3, **KEY), ValueError, "beta_head: alpha and beta must have one shape (got (2, 1, 4, 3), (3, 1, 4, 3))"),
+    (lambda: cp.normal_latents(SKIP_ODD, **LKEY), ValueError,
+     "normal_latents: skip needs an even channel count, loc then log_scale (got (2, 3, 3, 4))"),
+    (lambda: cp.beta_latents(SKIP_ODD, **LKEY), ValueError,
+     "beta_latents: skip needs an even channel count, loc then log_scale (got (2, 3, 3, 4))"),
+    (lambda: cp.beta_head(HEAD, HEAD, sqrt_reg=0.0, **KEY), ValueError, "beta_head: sqrt_reg must lie in (0, 0.5) (got 0.0)"),
+    (lambda: cp.beta_head(HEAD, HEAD, sqrt_reg=0.5, **KEY), ValueError, "beta_head: sqrt_reg must lie in (0, 0.5) (got 0.5)"),
+    (lambda: cp.beta_head(HEAD, HEAD, sqrt_reg=float("nan"), **KEY), ValueError, "beta_head: sqrt_reg must lie in (0, 0.5) (got nan)"),
+    # the size limits
+    (lambda: cp.truncated_normal_head(HEAD_HUGE, HEAD_HUGE, **KEY), ValueError,
+     "truncated_normal_head: at most 2^31 - 1 pixels per call (got 2147483648)"),
+    (lambda: cp.beta_head(HEAD_HUGE, HEAD_HUGE, **KEY), ValueError, "beta_head: at most 2^31 - 1 pixels per call (got 2147483648)"),
+    (lambda: cp.normal_latents(SKIP_HUGE, ns=2, level=0, **KEY), ValueError,
+     "normal_latents: at most 2^31 - 1 samples per call (got 2 x 1073741824)"),
+    (lambda: cp.beta_latents(SKIP_HUGE, ns=2, level=0, **KEY), ValueError,
+     "beta_latents: at most 2^31 - 1 samples per call (got 2 x 1073741824)"),
+    # the test operands
+    (lambda: cp.normal_latents(SKIP, _eps=SKIP, **LKEY), ValueError, "normal_latents: _eps must be [ns * B][C][H][W] on skip's device"),
+    (lambda: cp.beta_latents(SKIP, _extras=[], **LKEY), TypeError, "beta_latents: _extras must be a dict"),
+    # no CPU path
+    (lambda: cp.truncated_normal_head(HEAD, HEAD, **KEY), RadonLibraryError,
+     "truncated_normal_head: alpha and beta must be CUDA tensors on one device; there is no CPU path"),
+    (lambda: cp.truncated_normal_head(HEAD, HEAD.to("meta"), **KEY), RadonLibraryError,
+     "truncated_normal_head: alpha and beta must be CUDA tensors on one device; there is no CPU path"),
+    (lambda: cp.beta_head(HEAD, HEAD, **KEY), RadonLibraryError,
+     "beta_head: alpha and beta must be CUDA tensors on one device; there is no CPU path"),
+    (lambda: cp.normal_latents(SKIP, **LKEY), RadonLibraryError, "normal_latents: skip must be a CUDA tensor; there is no CPU path"),
+    (lambda: cp.beta_latents(SKIP, **LKEY), RadonLibraryError, "beta_latents: skip must be a CUDA tensor; there is no CPU path"),
 ]
 
 
