@@ -159,6 +159,11 @@ SIGNATURES = {
     "ctpvae_hmc_run_marginals_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp,
                                               _vp, _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp,
                                               ctypes.c_uint, _c_float, _c_float, _c_int, _vp, _vp, _vp, _vp]),
+    "ctpvae_hmc_diagnostics_lds_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "ctpvae_hmc_run_diagnostics_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp,
+                                                _vp, _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp,
+                                                _vp, ctypes.c_uint, _c_float, _c_float, _c_int, _vp, _vp, _vp, _c_int, _vp, _vp, _vp, _vp,
+                                                _vp]),
     "ctpvae_tn_head_fwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,
                                         _vp]),
     "ctpvae_tn_head_bwd_f32": (_c_int, [_vp, _vp, _c_int, _c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_uint, _vp, _vp, _vp, _vp,

@@ -6,8 +6,12 @@
     hmc_marginals(meas, mask, theta, pnm, *, bins, lo, width, ...)        the same run with the histograms, moments, acceptance and
                                                                           split R-hat of all chains accumulated inside the launches
                                                                           (csrc/hmc_marginals.hip); keeps no sample unless asked to
+    hmc_marginals(..., max_lag=L, cov=True)                               + the raw sums of the chains' autocovariance and of the
+                                                                          covariance between pixels (csrc/hmc_diagnostics.hip):
+                                                                          HmcMarginals.autocov / autocorr / ess / cov / corr
     python -m ct_pvae_amd.mcmc --save_path D -s STEPS -b BURNIN            bin/toy_mcmc_v2.py without its plots
-                               [--marginals [--no_trace] [--compare F]]    + hmc_marginals.npz; against a trainer's pixel_dist_K.npz
+                               [--marginals [--no_trace] [--compare F]     + hmc_marginals.npz; against a trainer's pixel_dist_K.npz
+                                [--ess_lags L] [--cov]]                    + effective sample size per pixel, covariance
 
 One 64-lane wave runs a whole chain inside one persistent kernel (csrc/hmc.hip states the density, the transition, the orders of
 the sums and the layout of the random numbers); this module validates, uploads the tables and loops over launches.  There is no
@@ -26,15 +30,19 @@ from .forward_functions import _stream_ptr, rotate_tables
 from .helper_functions import toy_dist
 from .marginals import _grid_args, hist_distance
 
-__all__ = ["hmc_sample", "hmc_marginals", "HmcMarginals", "split_rhat", "toy_dist", "MAX_STEPS_PER_LAUNCH"]
+__all__ = ["hmc_sample", "hmc_marginals", "HmcMarginals", "split_rhat", "autocov_from_sums", "toy_dist", "MAX_STEPS_PER_LAUNCH", "MAX_LAG"]
 
 # CTPVAE_HMC_MAX_STEPS of include/ctpvae_radon.h: the largest power of two that keeps one launch of the slowest shape measured with 5
 # leapfrog steps (8 x 8, 180 angles, 149 us per transition on the MI355X) under 100 ms (tools/time_hmc.py -> profiles/hmc_timing.txt).
 # The default steps_per_launch is this for up to 5 leapfrog steps and shrinks in proportion above, so that a default launch stays
 # near that time (the entry point's worst case, 32 leapfrog steps at 256 angles, costs 1.26 ms per transition).
 # hmc_marginals shares the cap: the longest launch of its kernel at that shape, with 254 bins, takes 78.9 ms (154 us per transition;
-# tools/time_hmc_marginals.py -> profiles/hmc_marginals_timing.txt).
+# tools/time_hmc_marginals.py -> profiles/hmc_marginals_timing.txt).  So does its max_lag / cov path: 80.05 ms with 64 lags and cov
+# (tools/time_hmc_diagnostics.py -> profiles/hmc_diagnostics_timing.txt).
 MAX_STEPS_PER_LAUNCH = 512
+# CTPVAE_HMC_MAX_LAG, and the LDS one workgroup can have on gfx950 (csrc/hmc_diagnostics.hip): what hmc_marginals(max_lag=, cov=) may ask
+MAX_LAG = 64
+LDS_BYTES_PER_WORKGROUP = 160 * 1024
 _MAX_ANGLES, _MAX_COMPONENTS, _MAX_LEAPFROGS = 256, 4, 32
 
 
@@ -63,7 +71,8 @@ def _prior_tables(prior, K, who="hmc_sample"):
 
 
 def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_steps, num_leapfrog_steps, step_size,
-               num_adaptation_steps, chains_per_object, initial_state, seed, first_chain, steps_per_launch, grid=None):
+               num_adaptation_steps, chains_per_object, initial_state, seed, first_chain, steps_per_launch, grid=None,
+               diag=None):
     """What hmc_sample and hmc_marginals share: every check on the values (grid = (bins, lo, width): the histogram's, checked last),
     then the device check, the uploads and the init launch.  Returns the run: sizes, the state and the model arguments of the run
     entry points (with the tensors they point into)."""
@@ -115,6 +124,16 @@ def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_st
             raise ValueError(f"{who}: initial_state must be positive and finite in every entry (points inside the simplex)")
     if grid is not None:
         grid = _grid_args(*grid)
+    if diag is not None:
+        # hmc_marginals' max_lag and cov: the range, then the LDS of one workgroup, both before anything touches the device
+        max_lag, cov = diag
+        if isinstance(max_lag, bool) or int(max_lag) != max_lag or not 0 <= int(max_lag) <= MAX_LAG:
+            raise ValueError(f"{who}: max_lag must be an integer 0 .. {MAX_LAG} (got {max_lag!r})")
+        diag = (int(max_lag), bool(cov))
+        need = lib.ctpvae_hmc_diagnostics_lds_bytes(N, A, grid[0], *diag)
+        if need > LDS_BYTES_PER_WORKGROUP:
+            raise ValueError(f"{who}: {N} x {N} pixels, {A} angles, bins={grid[0]}, max_lag={diag[0]}, cov={diag[1]} need {need} bytes of "
+                             f"LDS per chain, a workgroup has {LDS_BYTES_PER_WORKGROUP}: lower bins or max_lag, or turn cov off")
     if meas.device.type != "cuda" or mask.device != meas.device:
         raise _lib.RadonLibraryError(f"{who}: meas and mask must be CUDA tensors on one device; there is no CPU path")
     dev = meas.device
@@ -130,7 +149,7 @@ def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_st
         _lib.check(lib.ctpvae_hmc_init_f32(state.data_ptr(), C, cpo, *model, start.data_ptr() if start is not None else None,
                                            float(step_size), _stream_ptr()), "hmc_init")
     return types.SimpleNamespace(lib=lib, dev=dev, B=B, N=N, K=K, C=C, cpo=cpo, L=L, spl=spl, total=total, num_results=num_results,
-                                 num_burnin_steps=num_burnin_steps, state=state, model=model, grid=grid,
+                                 num_burnin_steps=num_burnin_steps, state=state, model=model, grid=grid, diag=diag,
                                  run_args=(L, num_burnin_steps, int(num_adaptation_steps), int(seed) & (2 ** 64 - 1)),
                                  first_chain=int(first_chain), keep=(meas_d, mask_d, start, T8, Tinv8, prior_d))
 
@@ -202,14 +221,52 @@ def split_rhat(s1, s2, n, chains_per_object):
         return np.sqrt(((n - 1) / n * W + Bn) / W)
 
 
+def autocov_from_sums(lag, head, ring, S, n):
+    """The centred biased autocovariance from the raw sums alone, float64 [C][Lm + 1][K].  lag [C][Lm + 1][K]: r_l = sum over j = l ..
+    n - 1 of x_j x_(j-l); head [C][Lm][K]: x_0 .. x_(Lm-1) (rows >= n unwritten); ring [C][Lm + 1][K]: x_j in slot j mod (Lm + 1) for
+    the last Lm + 1 steps; S [C][K]: the sum of all n values.  With m = S / n, H_l = S - (x_0 + .. + x_(l-1)) and T_l = S - (x_(n-1) +
+    .. + x_(n-l)):  c_l = (r_l - m (H_l + T_l) + (n - l) m^2) / n = sum_j (x_j - m)(x_(j-l) - m) / n exactly; c_l = 0 for l >= n."""
+    lag, S, n = np.asarray(lag, np.float64), np.asarray(S, np.float64), int(n)
+    head, ring = np.asarray(head, np.float64), np.asarray(ring, np.float64)
+    C, slots, K = lag.shape
+    m = S / n
+    out = np.zeros_like(lag)
+    first, last = np.zeros((C, K)), np.zeros((C, K))       # x_0 + .. + x_(l-1) and x_(n-1) + .. + x_(n-l)
+    for l in range(min(slots, n)):
+        if l:
+            first = first + head[:, l - 1]
+            last = last + ring[:, (n - l) % slots]
+        out[:, l] = (lag[:, l] - m * ((S - first) + (S - last)) + (n - l) * (m * m)) / n
+    return out
+
+
+def _geyer_ess(rho, n, M):
+    """Geyer's initial positive sequence over axis -2 of rho [..][Lm + 1][K] -> (ESS [..][K], truncated [..][K]); lags >= n count as 0."""
+    slots = rho.shape[-2]
+    rho = np.where((np.arange(slots) < n)[:, None], rho, 0.0)
+    pairs = slots // 2
+    P = rho[..., 0:2 * pairs:2, :] + rho[..., 1:2 * pairs:2, :]
+    keep = np.cumprod(P > 0, axis=-2).astype(bool)             # (a NaN pair is not positive)
+    total = np.where(keep, P, 0.0).sum(axis=-2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ess = np.where(keep[..., 0, :], M * n / (-1.0 + 2.0 * total), np.nan)
+    return ess, keep[..., -1, :]
+
+
 class HmcMarginals:
     """What hmc_marginals returns: the per-pixel marginals of C = B * chains_per_object chains on B objects of shape (N, N).
     On the device: hist int64 [B][K][bins + 2] (the rows of PixelMarginals.hist: below lo | the bins | at or above lo + bins * width,
     pooled over an object's chains), s1 and s2 float64 [2][C][K] (sum and sum of squares of the samples of each half of the kept steps,
     per chain), accepted int64 [C], step_size float32 [C] after the last step.  count = num_results * chains_per_object samples per
-    pixel and object.  samples and trace are hmc_sample's, or None."""
+    pixel and object.  samples and trace are hmc_sample's, or None.
 
-    def __init__(self, shape, bins, lo, width, num_results, chains_per_object, hist, s1, s2, accepted, step_size, samples=None, trace=None):
+    With hmc_marginals(max_lag=Lm >= 1): lag float64 [C][Lm + 1][K] (sum over the kept steps j >= l of x_j * x_(j-l), per chain and
+    pixel), ring float32 [C][Lm + 1][K] (the chain's last Lm + 1 kept values, step j in slot j mod (Lm + 1)) and head float32
+    [C][Lm][K] (its first Lm kept values); with cov=True: xx float64 [C][K][K] (sum over the kept steps of O_k * O_i).  None otherwise.
+    autocov(), autocorr(), ess(), ess_truncated(), cov() and corr() finish them on the host in float64."""
+
+    def __init__(self, shape, bins, lo, width, num_results, chains_per_object, hist, s1, s2, accepted, step_size, samples=None, trace=None,
+                 lag=None, ring=None, head=None, xx=None):
         self.shape = tuple(int(v) for v in shape)
         self.bins, self.lo, self.width = _grid_args(bins, lo, width)
         self.num_results, self.chains_per_object = int(num_results), int(chains_per_object)
@@ -223,6 +280,18 @@ class HmcMarginals:
         self.hist, self.s1, self.s2, self.accepted, self.step_size = hist, s1, s2, accepted, step_size
         self.samples, self.trace = samples, trace
         self.device = hist.device
+        self.max_lag = 0
+        if lag is not None or ring is not None or head is not None:
+            if lag is None or ring is None or head is None or lag.dim() != 3 or not 1 <= lag.shape[1] - 1 <= MAX_LAG:
+                raise ValueError("HmcMarginals: lag, ring and head come together, with 1 .. 64 lags")
+            self.max_lag = int(lag.shape[1]) - 1
+            if (tuple(lag.shape) != (C, self.max_lag + 1, K) or tuple(ring.shape) != (C, self.max_lag + 1, K)
+                    or tuple(head.shape) != (C, self.max_lag, K)):
+                raise ValueError(f"HmcMarginals: lag and ring [C][max_lag + 1][K] and head [C][max_lag][K] do not fit {C} chains, {K} pixels "
+                                 f"and {self.max_lag} lags")
+        if xx is not None and tuple(xx.shape) != (C, K, K):
+            raise ValueError(f"HmcMarginals: xx must be [{C}][{K}][{K}] (got {tuple(xx.shape)})")
+        self.lag, self.ring, self.head, self.xx = lag, ring, head, xx
 
     @property
     def edges(self):
@@ -265,12 +334,87 @@ class HmcMarginals:
             raise ValueError(f"HmcMarginals.rhat: split R-hat needs an even num_results >= 4 (got {self.num_results})")
         return split_rhat(self.s1.cpu().numpy(), self.s2.cpu().numpy(), self.num_results // 2, self.chains_per_object)
 
+    def _need_lags(self, what):
+        if self.max_lag < 1:
+            raise ValueError(f"HmcMarginals.{what}: the run kept no lagged products; call hmc_marginals with max_lag >= 1")
+
+    def autocov(self):
+        """float64 [C][max_lag + 1][K]: autocov_from_sums of every chain and pixel, the centred biased autocovariance of the chain's
+        num_results kept steps at lags 0 .. max_lag."""
+        self._need_lags("autocov")
+        return autocov_from_sums(self.lag.cpu().numpy(), self.head.cpu().numpy(), self.ring.cpu().numpy(), self._chain_sums()[0],
+                                 self.num_results)
+
+    def autocorr(self):
+        """float64 [C][max_lag + 1][K]: autocov() / its lag 0.  A chain whose pixel never moved has lag 0 equal to 0 and gets NaN, as
+        numpy evaluates it."""
+        c = self.autocov()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return c / c[:, :1]
+
+    def _ess(self, cross_chain):
+        """(ess, truncated) of ess() and ess_truncated()."""
+        self._need_lags("ess")
+        c, n, M = self.autocov(), self.num_results, self.chains_per_object
+        K = c.shape[2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if not cross_chain:
+                return _geyer_ess(c / c[:, :1], n, 1)
+            # W and var+ over whole chains: the within-chain variance (n - 1) and the variance of the chains' means
+            c = c.reshape(-1, M, self.max_lag + 1, K)
+            W = c[:, :, 0].mean(axis=1) * (n / (n - 1.0)) if n > 1 else np.full((c.shape[0], K), np.nan)
+            mu = self.chain_mean().reshape(-1, M, K)
+            Bn = mu.var(axis=1, ddof=1) if M > 1 else np.zeros_like(W)
+            var_plus = (n - 1.0) / n * W + Bn
+            rho = 1.0 - (W[:, None] - c.mean(axis=1)) / var_plus[:, None]
+            return _geyer_ess(rho, n, M)
+
+    def ess(self, cross_chain=True):
+        """Effective sample size by Geyer's initial positive sequence: with the pair sums P_m = rho_2m + rho_(2m+1), m = 0, 1, ..., over
+        the lags the run kept, truncated at the first pair that is not positive, ESS = M * n / (-1 + 2 * sum of the pairs kept); n =
+        num_results, lags >= n contribute nothing.  cross_chain=True: float64 [B][K], M = chains_per_object and rho_l = 1 - (W - mean_c
+        autocov_l,c) / var+, where W = mean_c autocov_0,c * n / (n - 1) and var+ = (n - 1) / n * W + var_c(chain means, ddof = 1) are
+        taken over WHOLE chains -- rhat() splits every chain in two halves, this does not, so the two do not share W or var+.  With one
+        chain per object var+ = (n - 1) / n * W.  cross_chain=False: float64 [C][K], every chain on its own with M = 1 and rho =
+        autocorr().  Where ess_truncated() is true the sum stopped at max_lag, not at a non-positive pair: the value is an upper
+        bound.  NaN where lag 0 carries no information (a pixel that never moved)."""
+        return self._ess(cross_chain)[0]
+
+    def ess_truncated(self, cross_chain=True):
+        """bool, the shape of ess(cross_chain): True where every pair sum up to max_lag was still positive, so that the sum was cut by
+        the lag window and ess() there is an upper bound."""
+        return self._ess(cross_chain)[1]
+
+    def cov(self):
+        """float64 [B][K][K]: the sample covariance (count - 1) between the pixels of an object over the count samples of all its
+        chains, from xx and the sums; the chains are added in ascending order.  NaN while count < 2."""
+        if self.xx is None:
+            raise ValueError("HmcMarginals.cov: the run kept no cross products; call hmc_marginals with cov=True")
+        K = self.shape[0] * self.shape[1]
+        X = np.cumsum(self.xx.cpu().numpy().reshape(-1, self.chains_per_object, K, K), axis=1)[:, -1]
+        t1 = self._object_sums()[0]
+        if self.count < 2:
+            return np.full(X.shape, np.nan)
+        return (X - t1[:, :, None] * t1[:, None, :] / self.count) / (self.count - 1)
+
+    def corr(self):
+        """float64 [B][K][K]: cov() / sqrt(its diagonal, outer); NaN in the rows and columns of a pixel that never moved."""
+        v = self.cov()
+        d = np.sqrt(np.maximum(np.einsum("bkk->bk", v), 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return v / (d[:, :, None] * d[:, None, :])
+
     def save(self, path):
         """One .npz: hist, s1, s2, accepted, step_size, edges, shape, bins, lo, width, num_results, chains_per_object, count and
-        head = "hmc"; with kept samples also samples and the trace's log_accept_ratio, is_accepted and target_log_prob."""
+        head = "hmc"; with kept samples also samples and the trace's log_accept_ratio, is_accepted and target_log_prob; with lags lag,
+        ring and lag_head (the first values: "head" names the file's kind); with cross products xx."""
         extra = {}
         if self.samples is not None:
             extra = dict(samples=self.samples.cpu().numpy(), **{k: v.cpu().numpy() for k, v in self.trace.items() if k != "step_size"})
+        if self.max_lag:
+            extra.update(lag=self.lag.cpu().numpy(), ring=self.ring.cpu().numpy(), lag_head=self.head.cpu().numpy())
+        if self.xx is not None:
+            extra["xx"] = self.xx.cpu().numpy()
         np.savez(path, hist=self.hist.cpu().numpy(), s1=self.s1.cpu().numpy(), s2=self.s2.cpu().numpy(),
                  accepted=self.accepted.cpu().numpy(), step_size=self.step_size.cpu().numpy(), edges=self.edges,
                  shape=np.asarray(self.shape, np.int64), bins=np.int64(self.bins), lo=np.float64(self.lo), width=np.float64(self.width),
@@ -291,7 +435,8 @@ class HmcMarginals:
                 trace = {k: t[k] for k in ("log_accept_ratio", "is_accepted", "target_log_prob")}
                 trace["step_size"] = t["step_size"].clone()
             m = cls(tuple(int(v) for v in f["shape"]), int(f["bins"]), float(f["lo"]), float(f["width"]), int(f["num_results"]),
-                    int(f["chains_per_object"]), t["hist"], t["s1"], t["s2"], t["accepted"], t["step_size"], samples, trace)
+                    int(f["chains_per_object"]), t["hist"], t["s1"], t["s2"], t["accepted"], t["step_size"], samples, trace, t.get("lag"),
+                    t.get("ring"), t.get("lag_head"), t.get("xx"))
             if int(f["count"]) != m.count:
                 raise ValueError(f"{path}: count {int(f['count'])} is not num_results * chains_per_object = {m.count}")
         return m
@@ -299,22 +444,37 @@ class HmcMarginals:
 
 def hmc_marginals(meas, mask, theta, pnm, *, bins=50, lo=0.005, width=0.01, keep_samples=False, prior=None, num_results,
                   num_burnin_steps=0, num_leapfrog_steps=5, step_size=6.5e-2, num_adaptation_steps=400, chains_per_object=1,
-                  initial_state=None, seed=0, first_chain=0, steps_per_launch=None):
+                  initial_state=None, seed=0, first_chain=0, steps_per_launch=None, max_lag=0, cov=False):
     """hmc_sample's run (every argument of it with its meaning and default; the same chains bit for bit) with the per-pixel marginals
     of ALL chains accumulated inside the sampler's launches (csrc/hmc_marginals.hip): per object a histogram on PixelMarginals' grid
     (bins, lo, width: the reference's np.arange(0.005, 0.51, 0.01) by default), per chain the float64 sum and sum of squares of each
     half of the kept steps, and the accepted steps.  Returns an HmcMarginals: mean(), std(), chain_mean(), accept_rate(), rhat().
     keep_samples=False stores nothing per step: samples and trace are None, and no allocation of the call grows with num_results.
     keep_samples=True returns hmc_sample's samples and trace beside the statistics.  A NaN sample counts in column 0 and makes its
-    chain's sums NaN."""
+    chain's sums NaN.
+
+    max_lag=Lm (1 .. MAX_LAG) and cov=True add, in the same launches (csrc/hmc_diagnostics.hip), per chain the float64 sums of the
+    products of every kept value with the chain's Lm values before it, and of every pair of pixels of a kept step: what
+    HmcMarginals.autocov(), autocorr(), ess(), ess_truncated() and cov(), corr() are finished from.  They cost (Lm + 1) * K * 12 + Lm * K * 4
+    and K * K * 8 bytes per chain, whatever num_results, and everything else of the result keeps its bits.  The sums sit in LDS during
+    a launch: a request above LDS_BYTES_PER_WORKGROUP (8 x 8 pixels with many angles, bins, lags and cov at once) raises ValueError
+    before any launch.  With the defaults (0, False) the call is the one it was."""
     r = _start_run("hmc_marginals", meas, mask, theta, pnm, prior=prior, num_results=num_results, num_burnin_steps=num_burnin_steps,
                    num_leapfrog_steps=num_leapfrog_steps, step_size=step_size, num_adaptation_steps=num_adaptation_steps,
                    chains_per_object=chains_per_object, initial_state=initial_state, seed=seed, first_chain=first_chain,
-                   steps_per_launch=steps_per_launch, grid=(bins, lo, width))
+                   steps_per_launch=steps_per_launch, grid=(bins, lo, width), diag=(max_lag, cov))
     bins, lo, width = r.grid
+    Lm, cov = r.diag
     hist = torch.zeros((r.B, r.K, bins + 2), dtype=torch.int64, device=r.dev)
     mom = torch.zeros((2, 2, r.C, r.K), dtype=torch.float64, device=r.dev)           # [half][moment][chain][pixel]
     accepted = torch.zeros(r.C, dtype=torch.int64, device=r.dev)
+    lag = ring = head = xx = None
+    if Lm:
+        lag = torch.zeros((r.C, Lm + 1, r.K), dtype=torch.float64, device=r.dev)
+        ring = torch.zeros((r.C, Lm + 1, r.K), dtype=torch.float32, device=r.dev)
+        head = torch.zeros((r.C, Lm, r.K), dtype=torch.float32, device=r.dev)
+    if cov:
+        xx = torch.zeros((r.C, r.K, r.K), dtype=torch.float64, device=r.dev)
     out = _per_step_outputs(r) if keep_samples else None
     L, keep_from, n_adapt, seed64 = r.run_args
     half_from = keep_from + r.num_results // 2
@@ -322,12 +482,16 @@ def hmc_marginals(meas, mask, theta, pnm, *, bins=50, lo=0.005, width=0.01, keep
         stream = _stream_ptr()
         for n, row in _launches(r):
             ptrs = [a[row].data_ptr() for a in out] if keep_samples else [None] * 4
-            _lib.check(r.lib.ctpvae_hmc_run_marginals_f32(r.state.data_ptr(), r.C, r.first_chain, r.cpo, *r.model, L, n, keep_from, n_adapt,
-                                                          seed64, *ptrs, half_from, lo, width, bins, hist.data_ptr(), mom.data_ptr(),
-                                                          accepted.data_ptr(), stream), "hmc_run_marginals")
+            args = (r.state.data_ptr(), r.C, r.first_chain, r.cpo, *r.model, L, n, keep_from, n_adapt, seed64, *ptrs, half_from, lo, width,
+                    bins, hist.data_ptr(), mom.data_ptr(), accepted.data_ptr())
+            if Lm or cov:
+                more = [a.data_ptr() if a is not None else None for a in (lag, ring, head, xx)]
+                _lib.check(r.lib.ctpvae_hmc_run_diagnostics_f32(*args, Lm, *more, stream), "hmc_run_diagnostics")
+            else:
+                _lib.check(r.lib.ctpvae_hmc_run_marginals_f32(*args, stream), "hmc_run_marginals")
     samples, trace = (out[0], _trace(r, *out[1:])) if keep_samples else (None, None)
     return HmcMarginals((r.N, r.N), bins, lo, width, r.num_results, r.cpo, hist, mom[:, 0], mom[:, 1], accepted,
-                        r.state[:, 2 * r.K - 1].clone(), samples, trace)
+                        r.state[:, 2 * r.K - 1].clone(), samples, trace, lag, ring, head, xx)
 
 
 def _load_pvae_hist(ap, path, m):
@@ -347,7 +511,9 @@ def main(argv=None):
     """bin/toy_mcmc_v2.py: example 0 of the toy dataset under --save_path, theta = [0, pi / 2], the used angles only, pnm = 1e3,
     5 leapfrog steps of 6.5e-2, 400 adaptation steps; writes posterior_prob_trace.npy [STEPS][4] (no plots).  --marginals: the run
     goes through hmc_marginals and hmc_marginals.npz is written too (--no_trace: and no sample is kept); --compare FILE: the
-    total-variation distance per pixel between FILE's histogram (a trainer's pixel_dist_K.npz) and this posterior's."""
+    total-variation distance per pixel between FILE's histogram (a trainer's pixel_dist_K.npz) and this posterior's; --ess_lags L:
+    prints the minimum and the median over the pixels of the cross-chain effective sample size (and says where it is only an upper
+    bound) and writes lag, ring and lag_head into the file; --cov: writes xx, the cross products of the pixels."""
     ap = argparse.ArgumentParser(description="HMC posterior of the 2 x 2 toy object")
     ap.add_argument("--save_path", required=True, help="directory with all_masks.npy and all_proj_samples.npy; the output goes there")
     ap.add_argument("-s", type=int, dest="number_of_steps", default=200000, help="number of kept steps")
@@ -362,9 +528,14 @@ def main(argv=None):
     ap.add_argument("--no_trace", action="store_true", help="with --marginals: keep no samples, write no posterior_prob_trace.npy")
     ap.add_argument("--compare", metavar="FILE", help="with --marginals: a pixel_dist_K.npz of the trainer on the same grid; prints the "
                     "total-variation distance per pixel and writes hmc_vs_pvae.npy")
+    ap.add_argument("--ess_lags", type=int, default=0, metavar="L", help="with --marginals: accumulate the autocovariance up to lag L "
+                    f"(1 .. {MAX_LAG}) and print the effective sample size per pixel")
+    ap.add_argument("--cov", action="store_true", help="with --marginals: accumulate the covariance between the pixels")
     args = ap.parse_args(argv)
-    if (args.no_trace or args.compare) and not args.marginals:
-        ap.error("--no_trace and --compare need --marginals")
+    if (args.no_trace or args.compare or args.ess_lags or args.cov) and not args.marginals:
+        ap.error("--no_trace, --compare, --ess_lags and --cov need --marginals")
+    if not 0 <= args.ess_lags <= MAX_LAG:
+        ap.error(f"--ess_lags must be 0 .. {MAX_LAG}")
     mask = np.load(os.path.join(args.save_path, "all_masks.npy"))[0].astype(np.float32)
     meas = np.load(os.path.join(args.save_path, "all_proj_samples.npy"))[0].astype(np.float32)
     if args.marginals:
@@ -377,13 +548,18 @@ def main(argv=None):
                num_adaptation_steps=400, chains_per_object=args.chains, seed=args.seed)
     problem = (torch.from_numpy(meas[used]).to(dev), torch.from_numpy(mask[used]).to(dev), theta[used], 1e3)
     if args.marginals:
-        m = hmc_marginals(*problem, bins=bins, lo=lo, width=width, keep_samples=not args.no_trace, **run)
+        m = hmc_marginals(*problem, bins=bins, lo=lo, width=width, keep_samples=not args.no_trace, max_lag=args.ess_lags, cov=args.cov,
+                          **run)
         m.save(os.path.join(args.save_path, "hmc_marginals.npz"))
         samples = m.samples
         rate = m.accept_rate()
         print(f"{m.count} samples per pixel; acceptance {rate.min():.3f} .. {rate.max():.3f}; mean {m.mean()[0].ravel()}")
         if m.num_results >= 4 and m.num_results % 2 == 0:
             print(f"split R-hat per pixel {m.rhat()[0]}")
+        if m.max_lag:
+            ess, cut = m.ess()[0], m.ess_truncated()[0]
+            print(f"ESS per pixel {ess}: minimum {np.nanmin(ess):.1f}, median {np.nanmedian(ess):.1f} of {m.count} samples"
+                  + (f"; still positive at lag {m.max_lag} in {int(cut.sum())} pixels: upper bounds there" if cut.any() else ""))
         if pvae is not None:
             d = hist_distance(pvae, m.hist[0].cpu().numpy())
             print(f"total-variation distance to {args.compare} per pixel {d}")

@@ -720,6 +720,31 @@ int ctpvae_hmc_run_marginals_f32(float *state_dev, int C, unsigned first_chain, 
                                  float width, int bins, long long *hist_dev, double *mom_dev, long long *accepted_dev,
                                  ctpvae_stream_t stream);
 
+/* ---- ctpvae_hmc_run_marginals_f32 with the raw sums of the chains' autocovariance and of the covariance between pixels accumulated in
+ * the same launch (csrc/hmc_diagnostics.hip states the layout and the orders).  Every argument of _run_marginals_f32 with its meaning;
+ * with max_lag = 0 and xx_dev NULL the three arrays get _run_marginals_f32's bits.  For kept step j (index n_keep_from + j), pixel
+ * k < K and x = O_k, after the marginals' updates:
+ *   max_lag = Lm, 1 .. CTPVAE_HMC_MAX_LAG:  ring_dev [C][Lm + 1][K] fp32 slot j mod (Lm + 1) = x;  head_dev [C][Lm][K] fp32 row j = x while
+ *     j < Lm;  lag_dev [C][Lm + 1][K] float64 row l += (double)x * (double)(the chain's kept value of pixel k at step j - l), l = 0 ..
+ *     min(j, Lm) ascending.  Lm = 0: the three pointers are NULL.
+ *   xx_dev [C][K][K] float64 (or NULL: off):  [k][i] += (double)O_k * (double)O_i, i ascending; [k][i] and [i][k] are equal by bits.
+ * Every sum is strictly sequential over the chain's own kept steps in ascending order, one rounding per step (the products are exact),
+ * however the run is cut into launches and its chains into calls.  A launch ADDS: zero all arrays before the first (lag and xx 8-byte
+ * aligned).
+ *   _diagnostics_lds_bytes(N, A, bins, max_lag, cov): dynamic LDS of one workgroup (host only): _marginals_lds_bytes rounded up to 8, then
+ *     (Lm + 1) * K * 4 (rounded up to 8) + (Lm + 1) * K * 8 bytes when Lm > 0 and K * K * 8 when cov != 0.  _run_diagnostics_f32 refuses a
+ *     request above the 163,840 bytes a workgroup has on gfx950 (8 x 8, 256 angles, 254 bins, 64 lags and cov: 205,856) before any
+ *     launch; lower bins or max_lag, or turn cov off. */
+#define CTPVAE_HMC_MAX_LAG 64
+long long ctpvae_hmc_diagnostics_lds_bytes(int N, int A, int bins, int max_lag, int cov);
+int ctpvae_hmc_run_diagnostics_f32(float *state_dev, int C, unsigned first_chain, int chains_per_object, int N, const float *T8_dev,
+                                   const float *Tinv8_dev, int A, const float *mask_dev, const float *meas_dev, float pnm, int M,
+                                   const float *logw_dev, const float *alpha_dev, const float *lbeta_dev, int L, int n_steps,
+                                   unsigned n_keep_from, unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev,
+                                   float *lar_out_dev, float *accepted_out_dev, float *target_out_dev, unsigned n_half_from, float lo,
+                                   float width, int bins, long long *hist_dev, double *mom_dev, long long *accepted_dev, int max_lag,
+                                   double *lag_dev, float *ring_dev, float *head_dev, double *xx_dev, ctpvae_stream_t stream);
+
 /* ---- the P-VAE decoder's TruncatedNormal output head (ctvae/helper_functions.py:198-201, :273): sample, log-density and its
  * per-object sum in ONE launch, their gradients in one more (csrc/head.hip states the function, the order of the sum and the layout
  * of the random numbers).  alpha_dev, beta_dev [n][pix]: the decoder's raw outputs, pix = X * Y pixels per object, fp32.
