@@ -155,6 +155,13 @@ SIGNATURES = {
                                      _c_float, _vp]),
     "ctpvae_hmc_run_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp,
                                     _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp]),
+    "ctpvae_hmc_wg_state_floats": (_c_int, [_c_int]),
+    "ctpvae_hmc_wg_lds_bytes": (ctypes.c_longlong, [_c_int, _c_int]),
+    "ctpvae_hmc_wg_resident_chains": (_c_int, [_c_int, _c_int, _vp]),
+    "ctpvae_hmc_wg_init_f32": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp, _vp, _vp,
+                                        _c_float, _vp]),
+    "ctpvae_hmc_wg_run_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp, _vp,
+                                       _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp, _vp]),
     "ctpvae_hmc_marginals_lds_bytes": (ctypes.c_longlong, [_c_int, _c_int, _c_int]),
     "ctpvae_hmc_run_marginals_f32": (_c_int, [_vp, _c_int, ctypes.c_uint, _c_int, _c_int, _vp, _vp, _c_int, _vp, _vp, _c_float, _c_int, _vp,
                                               _vp, _vp, _c_int, _c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_ulonglong, _vp, _vp, _vp, _vp,

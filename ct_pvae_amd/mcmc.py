@@ -14,10 +14,12 @@
                                 [--ess_lags L] [--cov]]                    + effective sample size per pixel, covariance
 
 One 64-lane wave runs a whole chain inside one persistent kernel (csrc/hmc.hip states the density, the transition, the orders of
-the sums and the layout of the random numbers); this module validates, uploads the tables and loops over launches.  There is no
-CPU path.
+the sums and the layout of the random numbers); this module validates, uploads the tables and loops over launches.  With
+hmc_sample(form="workgroup") a workgroup of up to 16 waves runs the chain, one pixel per thread, for objects of up to 32 x 32 pixels
+(csrc/hmc_wg.hip).  There is no CPU path.
 """
 import argparse
+import ctypes
 import math
 import os
 import types
@@ -30,7 +32,8 @@ from .forward_functions import _stream_ptr, rotate_tables
 from .helper_functions import toy_dist
 from .marginals import _grid_args, hist_distance
 
-__all__ = ["hmc_sample", "hmc_marginals", "HmcMarginals", "split_rhat", "autocov_from_sums", "toy_dist", "MAX_STEPS_PER_LAUNCH", "MAX_LAG"]
+__all__ = ["hmc_sample", "hmc_marginals", "HmcMarginals", "split_rhat", "autocov_from_sums", "toy_dist", "MAX_STEPS_PER_LAUNCH", "MAX_STEPS_PER_LAUNCH_WG",
+           "MAX_LAG"]
 
 # CTPVAE_HMC_MAX_STEPS of include/ctpvae_radon.h: the largest power of two that keeps one launch of the slowest shape measured with 5
 # leapfrog steps (8 x 8, 180 angles, 149 us per transition on the MI355X) under 100 ms (tools/time_hmc.py -> profiles/hmc_timing.txt).
@@ -44,6 +47,16 @@ MAX_STEPS_PER_LAUNCH = 512
 MAX_LAG = 64
 LDS_BYTES_PER_WORKGROUP = 160 * 1024
 _MAX_ANGLES, _MAX_COMPONENTS, _MAX_LEAPFROGS = 256, 4, 32
+# The cap of hmc_sample(form="workgroup") (csrc/hmc_wg.hip), by the same rule: the largest power of two, at most 512, that keeps one
+# launch of a full residency of chains of the slowest shape measured with 5 leapfrog steps under 100 ms on the MI355X.  Measured
+# (tools/time_hmc_wg.py -> profiles/hmc_wg_timing.txt; it starts at 8 transitions per launch and doubles only while the projection
+# stays under 100 ms), per transition inside a launch, 1 chain / one full residency of chains: 9 x 9 at 20 angles 23.9 / 33.6 us
+# (2,560 chains), 16 x 16 at 20 angles 30.5 / 38.7 us (1,280), 16 x 16 at 90 angles 82.3 / 82.4 us (256), 32 x 32 at 20 angles 51.1 /
+# 51.3 us (256).  The slowest, 82.4 us, makes a launch of 512 transitions 42.2 ms: the cap is 512, and the default shrinks with the
+# leapfrog count above 5 as the wave form's does.  (Shapes beyond the table are not measured: a transition's time grows with the
+# angle count, so a run with many more angles than these should pass a smaller steps_per_launch.)
+MAX_STEPS_PER_LAUNCH_WG = 512
+_MAX_N_WG = 32
 
 
 def _lgamma64(a):
@@ -70,13 +83,30 @@ def _prior_tables(prior, K, who="hmc_sample"):
     return np.log(weights).astype(np.float32), alpha.astype(np.float32), lbeta.astype(np.float32)
 
 
+def _wg_pieces(C, cpo, cap):
+    """The workgroup form's launches over C chains, at most cap chains each: (first chain, chains, chains per object of the launch,
+    its first object).  A launch holds whole objects, or chains of one object alone (then all its chains share that object)."""
+    c = 0
+    while c < C:
+        obj, within = divmod(c, cpo)
+        if within == 0 and cap >= cpo:
+            n, per = min(cap, C - c) // cpo * cpo, cpo
+        else:
+            n = per = min(cap, cpo - within)
+        yield c, n, per, obj
+        c += n
+
+
 def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_steps, num_leapfrog_steps, step_size,
                num_adaptation_steps, chains_per_object, initial_state, seed, first_chain, steps_per_launch, grid=None,
-               diag=None):
+               diag=None, form="wave", chains_per_launch=None):
     """What hmc_sample and hmc_marginals share: every check on the values (grid = (bins, lo, width): the histogram's, checked last),
     then the device check, the uploads and the init launch.  Returns the run: sizes, the state and the model arguments of the run
     entry points (with the tensors they point into)."""
     lib = _lib.load()
+    if form not in ("wave", "workgroup"):
+        raise ValueError(f"{who}: form must be 'wave' or 'workgroup' (got {form!r})")
+    wg = form == "workgroup"
     if not (isinstance(meas, torch.Tensor) and isinstance(mask, torch.Tensor)):
         raise TypeError(f"{who}: meas and mask must be torch tensors")
     if meas.dim() == 2:
@@ -86,8 +116,11 @@ def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_st
     B, A, N = meas.shape
     K = N * N
     th = np.asarray(theta.detach().cpu() if isinstance(theta, torch.Tensor) else theta, dtype=np.float32).reshape(-1)
-    if K > 64:
-        raise ValueError(f"{who}: objects of at most 64 pixels, one per lane (got N={N}: {K} pixels)")
+    if K > 64 and not wg:
+        raise ValueError(f"{who}: objects of at most 64 pixels, one per lane (got N={N}: {K} pixels)"
+                         + ("; form='workgroup' takes up to 32 x 32" if who == "hmc_sample" else ""))
+    if N > _MAX_N_WG:
+        raise ValueError(f"{who}: form='workgroup' takes objects of at most {_MAX_N_WG} x {_MAX_N_WG} pixels, one per thread (got N={N})")
     if N < 2:
         raise ValueError(f"{who}: the object needs at least 2 x 2 pixels")
     if th.size != A or tuple(mask.shape) != (B, A):
@@ -104,9 +137,18 @@ def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_st
         raise ValueError(f"{who}: 1 .. {_MAX_LEAPFROGS} leapfrog steps (got {L})")
     if not float(step_size) > 0 or not float(pnm) > 0:
         raise ValueError(f"{who}: step_size and pnm must be positive")
-    spl = max(1, MAX_STEPS_PER_LAUNCH * 5 // max(L, 5)) if steps_per_launch is None else int(steps_per_launch)
-    if not 1 <= spl <= MAX_STEPS_PER_LAUNCH:
-        raise ValueError(f"{who}: steps_per_launch must be 1 .. {MAX_STEPS_PER_LAUNCH} (got {spl})")
+    spl_cap = MAX_STEPS_PER_LAUNCH_WG if wg else MAX_STEPS_PER_LAUNCH
+    spl = max(1, spl_cap * 5 // max(L, 5)) if steps_per_launch is None else int(steps_per_launch)
+    if not 1 <= spl <= spl_cap:
+        raise ValueError(f"{who}: steps_per_launch must be 1 .. {spl_cap} (got {spl})")
+    if chains_per_launch is not None and (not wg or int(chains_per_launch) < 1):
+        raise ValueError(f"{who}: chains_per_launch is a positive number of chains, for form='workgroup' alone (got {chains_per_launch!r})")
+    if wg:
+        # the tap tables of a launch sit in LDS: refused here, before anything touches the device
+        need = lib.ctpvae_hmc_wg_lds_bytes(N, A)
+        if need > LDS_BYTES_PER_WORKGROUP:
+            raise ValueError(f"{who}: {N} x {N} pixels at {A} angles need {need} bytes of LDS per chain, a workgroup has "
+                             f"{LDS_BYTES_PER_WORKGROUP}: fewer angles")
     total = num_burnin_steps + num_results
     if total >= 2 ** 32:
         raise ValueError(f"{who}: the step index is 32 bits wide")
@@ -145,10 +187,24 @@ def _start_run(who, meas, mask, theta, pnm, *, prior, num_results, num_burnin_st
     state = forward_functions._new_output((C, 2 * K + 1), torch.float32, dev)
     model = (N, T8.data_ptr(), Tinv8.data_ptr(), A, mask_d.data_ptr(), meas_d.data_ptr(), float(pnm), logw.size, prior_d[0].data_ptr(),
              prior_d[1].data_ptr(), prior_d[2].data_ptr())
+    pieces = None
     with torch.cuda.device(dev):
-        _lib.check(lib.ctpvae_hmc_init_f32(state.data_ptr(), C, cpo, *model, start.data_ptr() if start is not None else None,
-                                           float(step_size), _stream_ptr()), "hmc_init")
+        if wg:
+            # at most as many workgroups in a launch as the device keeps resident at once
+            cap = ctypes.c_int(0)
+            _lib.check(lib.ctpvae_hmc_wg_resident_chains(N, A, ctypes.byref(cap)), "hmc_wg_resident_chains")
+            cap = cap.value if chains_per_launch is None else min(cap.value, int(chains_per_launch))
+            pieces = list(_wg_pieces(C, cpo, cap))
+            for c0, n, per, obj in pieces:
+                m = list(model)
+                m[4], m[5] = mask_d[obj].data_ptr(), meas_d[obj].data_ptr()
+                _lib.check(lib.ctpvae_hmc_wg_init_f32(state[c0].data_ptr(), n, per, *m, start[c0].data_ptr() if start is not None else None,
+                                                      float(step_size), _stream_ptr()), "hmc_wg_init")
+        else:
+            _lib.check(lib.ctpvae_hmc_init_f32(state.data_ptr(), C, cpo, *model, start.data_ptr() if start is not None else None,
+                                               float(step_size), _stream_ptr()), "hmc_init")
     return types.SimpleNamespace(lib=lib, dev=dev, B=B, N=N, K=K, C=C, cpo=cpo, L=L, spl=spl, total=total, num_results=num_results,
+                                 pieces=pieces, mask_d=mask_d, meas_d=meas_d,
                                  num_burnin_steps=num_burnin_steps, state=state, model=model, grid=grid, diag=diag,
                                  run_args=(L, num_burnin_steps, int(num_adaptation_steps), int(seed) & (2 ** 64 - 1)),
                                  first_chain=int(first_chain), keep=(meas_d, mask_d, start, T8, Tinv8, prior_d))
@@ -172,8 +228,10 @@ def _trace(r, lar, acc, tgt):
 
 
 def hmc_sample(meas, mask, theta, pnm, *, prior=None, num_results, num_burnin_steps=0, num_leapfrog_steps=5, step_size=6.5e-2,
-               num_adaptation_steps=400, chains_per_object=1, initial_state=None, seed=0, first_chain=0, steps_per_launch=None):
-    """Posterior samples of N x N objects (N * N <= 64) on the simplex given sparse noisy sinograms, by HMC on the GPU.
+               num_adaptation_steps=400, chains_per_object=1, initial_state=None, seed=0, first_chain=0, steps_per_launch=None,
+               form="wave", chains_per_launch=None):
+    """Posterior samples of N x N objects (N * N <= 64; up to 32 x 32 with form="workgroup") on the simplex given sparse noisy
+    sinograms, by HMC on the GPU.
 
     meas [A][N] or [B][A][N] and mask [A] or [B][A]: CUDA float tensors (create_all_masks' outputs); theta [A] radians; pnm: the
     Poisson noise multiplier.  prior: (weights [M], concentrations [M][K]) of a mixture of M <= 4 Dirichlets, default toy_dist().
@@ -183,20 +241,41 @@ def hmc_sample(meas, mask, theta, pnm, *, prior=None, num_results, num_burnin_st
     image of 0).  The step size adapts during the first num_adaptation_steps steps (burn-in included), per chain.  steps_per_launch
     (1 .. MAX_STEPS_PER_LAUNCH) defaults to that cap, divided by num_leapfrog_steps / 5 above 5 leapfrog steps.
 
+    form="wave" (the default): one 64-lane wave per chain, csrc/hmc.hip.  form="workgroup": one workgroup of ceil(K / 64) waves per
+    chain, one pixel per thread, 2 <= N <= 32 (csrc/hmc_wg.hip): the same target, transition, random numbers and outputs, and for
+    N <= 8 the same bits.  Its tap tables sit in LDS, so an (N, A) above LDS_BYTES_PER_WORKGROUP (32 x 32 beyond 46 angles) raises
+    ValueError before any launch; steps_per_launch is 1 .. MAX_STEPS_PER_LAUNCH_WG there.  A launch of that form holds at most as
+    many chains as the device keeps resident at once (multiprocessors x the occupancy query); further launches take the rest, which
+    changes no bit.  chains_per_launch (developers) lowers that number.
+
     Returns (samples [num_results][C][K], trace) with trace = {"log_accept_ratio", "is_accepted", "target_log_prob":
     [num_results][C], "step_size": [C] after the last step}."""
     r = _start_run("hmc_sample", meas, mask, theta, pnm, prior=prior, num_results=num_results, num_burnin_steps=num_burnin_steps,
                    num_leapfrog_steps=num_leapfrog_steps, step_size=step_size, num_adaptation_steps=num_adaptation_steps,
                    chains_per_object=chains_per_object, initial_state=initial_state, seed=seed, first_chain=first_chain,
-                   steps_per_launch=steps_per_launch)
-    samples, lar, acc, tgt = _per_step_outputs(r)
+                   steps_per_launch=steps_per_launch, form=form, chains_per_launch=chains_per_launch)
+    samples, lar, acc, tgt = out = _per_step_outputs(r)
     L, keep_from, n_adapt, seed64 = r.run_args
     with torch.cuda.device(r.dev):
         stream = _stream_ptr()
-        for n, row in _launches(r):
-            _lib.check(r.lib.ctpvae_hmc_run_f32(r.state.data_ptr(), r.C, r.first_chain, r.cpo, *r.model, L, n, keep_from, n_adapt, seed64,
-                                                samples[row].data_ptr(), lar[row].data_ptr(), acc[row].data_ptr(), tgt[row].data_ptr(),
-                                                stream), "hmc_run")
+        for i, (n, row) in enumerate(_launches(r)):
+            if r.pieces is None:
+                _lib.check(r.lib.ctpvae_hmc_run_f32(r.state.data_ptr(), r.C, r.first_chain, r.cpo, *r.model, L, n, keep_from, n_adapt,
+                                                    seed64, samples[row].data_ptr(), lar[row].data_ptr(), acc[row].data_ptr(),
+                                                    tgt[row].data_ptr(), stream), "hmc_run")
+                continue
+            kept = max(0, i * r.spl + n - max(i * r.spl, r.num_burnin_steps))      # the rows this launch stores
+            for c0, nc, per, obj in r.pieces:
+                # the entry point stores rows of ITS chains: straight into the outputs when the launch holds all of them
+                dst = [a[row:] for a in out] if nc == r.C else [
+                    forward_functions._new_output((max(kept, 1), nc) + a.shape[2:], torch.float32, r.dev) for a in out]
+                m = list(r.model)
+                m[4], m[5] = r.mask_d[obj].data_ptr(), r.meas_d[obj].data_ptr()
+                _lib.check(r.lib.ctpvae_hmc_wg_run_f32(r.state[c0].data_ptr(), nc, r.first_chain + c0, per, *m, L, n, keep_from, n_adapt,
+                                                       seed64, *(a.data_ptr() for a in dst), stream), "hmc_wg_run")
+                if nc != r.C and kept:
+                    for a, d in zip(out, dst):
+                        a[row:row + kept, c0:c0 + nc] = d[:kept]
     return samples, _trace(r, lar, acc, tgt)
 
 
@@ -458,7 +537,9 @@ def hmc_marginals(meas, mask, theta, pnm, *, bins=50, lo=0.005, width=0.01, keep
     HmcMarginals.autocov(), autocorr(), ess(), ess_truncated() and cov(), corr() are finished from.  They cost (Lm + 1) * K * 12 + Lm * K * 4
     and K * K * 8 bytes per chain, whatever num_results, and everything else of the result keeps its bits.  The sums sit in LDS during
     a launch: a request above LDS_BYTES_PER_WORKGROUP (8 x 8 pixels with many angles, bins, lags and cov at once) raises ValueError
-    before any launch.  With the defaults (0, False) the call is the one it was."""
+    before any launch.  With the defaults (0, False) the call is the one it was.
+
+    This call runs the wave form only (N * N <= 64): hmc_sample's form="workgroup" has no marginals or diagnostics yet."""
     r = _start_run("hmc_marginals", meas, mask, theta, pnm, prior=prior, num_results=num_results, num_burnin_steps=num_burnin_steps,
                    num_leapfrog_steps=num_leapfrog_steps, step_size=step_size, num_adaptation_steps=num_adaptation_steps,
                    chains_per_object=chains_per_object, initial_state=initial_state, seed=seed, first_chain=first_chain,

@@ -694,6 +694,31 @@ int ctpvae_hmc_run_f32(float *state_dev, int C, unsigned first_chain, int chains
                        unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev, float *lar_out_dev,
                        float *accepted_out_dev, float *target_out_dev, ctpvae_stream_t stream);
 
+/* ---- the same sampler for objects beyond 64 pixels: one workgroup of W = ceil(K / 64) waves per chain, one pixel per thread, 2 <= N <= 32
+ * (csrc/hmc_wg.hip states how the orders of the sums generalise; everything else -- target, transition, random numbers, state -- is
+ * csrc/hmc.hip's).  _wg_init_f32 and _wg_run_f32 take the arguments of ctpvae_hmc_init_f32 and ctpvae_hmc_run_f32 with their meaning and
+ * limits, except 2 <= N <= 32; for N <= 8 (one wave) they give those entry points' bits.  The tap tables of a launch sit in LDS: an
+ * (N, A) whose request exceeds the 163,840 bytes a workgroup has on gfx950 is refused before any launch (32 x 32 admits 46 angles, 23 x 23
+ * 86, 16 x 16 168, 12 x 12 and smaller all 256).  One launch should hold no more chains than the device keeps resident (_wg_resident_chains); the caller
+ * cuts C into launches -- state_dev, start_dev and the outputs of a launch are those of ITS chains, first_chain the id of its first.
+ *   _wg_state_floats(K): 2K + 1 for 4 <= K <= 1024.
+ *   _wg_lds_bytes(N, A): dynamic LDS of one workgroup (host only), also where it exceeds what a workgroup has.
+ *   _wg_resident_chains(N, A, chains_out): multiprocessors of the current device x the occupancy query of the run kernel at this block size
+ *     and LDS request (at least 1 per multiprocessor).
+ * CTPVAE_HMC_MAX_STEPS bounds n_steps here too; ct_pvae_amd/mcmc.py's MAX_STEPS_PER_LAUNCH_WG is the measured cap of this form
+ * (profiles/hmc_wg_timing.txt). */
+int ctpvae_hmc_wg_state_floats(int K);
+long long ctpvae_hmc_wg_lds_bytes(int N, int A);
+int ctpvae_hmc_wg_resident_chains(int N, int A, int *chains_out);
+int ctpvae_hmc_wg_init_f32(float *state_dev, int C, int chains_per_object, int N, const float *T8_dev, const float *Tinv8_dev, int A,
+                           const float *mask_dev, const float *meas_dev, float pnm, int M, const float *logw_dev, const float *alpha_dev,
+                           const float *lbeta_dev, const float *start_dev, float step_size, ctpvae_stream_t stream);
+int ctpvae_hmc_wg_run_f32(float *state_dev, int C, unsigned first_chain, int chains_per_object, int N, const float *T8_dev,
+                          const float *Tinv8_dev, int A, const float *mask_dev, const float *meas_dev, float pnm, int M,
+                          const float *logw_dev, const float *alpha_dev, const float *lbeta_dev, int L, int n_steps, unsigned n_keep_from,
+                          unsigned num_adaptation_steps, unsigned long long seed, float *samples_out_dev, float *lar_out_dev,
+                          float *accepted_out_dev, float *target_out_dev, ctpvae_stream_t stream);
+
 /* ---- the HMC sampler with the chains' per-pixel marginals accumulated inside the launch (csrc/hmc_marginals.hip states the layout and
  * the orders): the transitions of ctpvae_hmc_run_f32 bit for bit -- same arguments, same state (ctpvae_hmc_init_f32 starts it), same
  * random numbers -- and, for every kept step (index >= n_keep_from) and pixel k < K, with O the sample _run_f32 would store:
